@@ -9,20 +9,28 @@ gpmpc_predict_mean_var, which --two-calls times instead; the line carries the ot
 ranks.  With --gpus N every rank runs its own model / test batch on its own GPU (independent GP
 objects shard trivially, no data-path collective): weak scaling.  `python bench.py --gpus N` launches its N ranks
 itself (one process per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rank 0 prints the line); under
-torch.distributed.run the ranks it finds in the environment are used.  For N > 1 the line also carries `restart_shard`:
+torch.distributed.run the ranks it finds in the environment are used.
+
+A plain run sets up, warms up, times --steps steps (no event brackets in them) and prints the headline line; --dump-outputs DIR
+also writes the last timed step's mean and variance as DIR/mean.npy, DIR/var.npy (float64; the inputs are seeded, so two
+builds can be compared output for output).  Everything else is measured only with --full, after the timed region, which then
+carries the vargemm bracket the roofline needs: `roofline`, `cholesky`, the phase split (a second, bracketed pass), the other
+step API, `cpu_baseline` / parity (unless --no-cpu-baseline) and, for N > 1, `restart_shard`:
 the ONE part of the path that shards (BASELINE config C4) -- 64 seeded restarts of the NLL minimisation, restart r on
 rank r mod N, ONE ncclAllGather of the (NLL, theta) table inside gpmpc_train_multistart -- as restarts/s (strong
-scaling) with `rccl_ranks` = ncclCommCount of the communicator that carried it.  For N = 1 the line carries `secondary`
+scaling) with `rccl_ranks` = ncclCommCount of the communicator that carried it; for N = 1, unless --no-secondary, `secondary`
 (after the timed C2 region): two steps of C3 (the three methods in lock-step, gpmpc_rollout_multi; `rollout_hbm`), one of C4 (with a
 flop-counted `roofline`), `c5` (Nt = 30 shooting nodes per call: value + Jacobian + TA covariance, 50 calls, at C3 size and at the
 reference's car-model size) and `b1` (B = 1 streaming predictions on the fitted C2 model), each with its HBM roofline.
 
 --config C3 (secondary, same JSON shape; the default and the headline stay C2): BASELINE.json configs[2] --
 6-output GP, N=8192, d=8: one STEP = fit of all outputs with K^-1 + a 30-step uncertainty propagation with each
-of 'ME', 'TA', 'EM' (gpmpc_rollout); `value` = propagation steps/s over whole steps (fit included).
+of 'ME', 'TA', 'EM' (gpmpc_rollout); `value` = propagation steps/s over whole steps (fit included); --dump-outputs writes
+rollout_<method>_mean / _cov.
 --config C4: BASELINE.json configs[3] -- hyper-parameter training at N=4096, d=6: one STEP = 64 seeded restarts (4 L-BFGS
 iterations each) of `gpmpc_train_multistart`, restart r on rank r mod world, the (NLL, theta) table exchanged by ONE
-ncclAllGather over an RCCL communicator the library creates (strong scaling: the 64 restarts are fixed); `value` = restarts/s.
+ncclAllGather over an RCCL communicator the library creates (strong scaling: the 64 restarts are fixed); `value` = restarts/s;
+--dump-outputs writes the gathered table (nll, theta) and the arg-min hyper-parameters (hyper).
 
 Extra objects on the JSON line:
   roofline     -- the dominant kernel (variance GEMM V = L^-1 Ks with fused column sums of squares):
@@ -291,8 +299,9 @@ def timed(rk, h, step, steps, warmup, profile=True, phases=None):
     return rk.max_over_ranks(elapsed), prof
 
 
-def run_c3(rk, steps, warmup, N=8192):
-    """BASELINE config C3: 6-output GP, N = 8192, d = 8; step = fit (with K^-1) + 30-step ME / TA / EM propagation."""
+def run_c3(rk, steps, warmup, N=8192, dumped=None):
+    """BASELINE config C3: 6-output GP, N = 8192, d = 8; step = fit (with K^-1) + 30-step ME / TA / EM propagation.
+    dumped: filled with the last timed step's roll-outs (mean and covariance per method) for --dump-outputs."""
     import numpy as np
     from gp_mpc_amd._lib import Handle
     from gp_mpc_amd.synthetic import synthetic_problem
@@ -317,6 +326,9 @@ def run_c3(rk, steps, warmup, N=8192):
             res[m] = (mm[i], cc[i])
 
     elapsed, prof = timed(rk, h, step, steps, warmup)
+    if dumped is not None:
+        for m in ('ME', 'TA', 'EM'):
+            dumped['rollout_%s_mean' % m], dumped['rollout_%s_cov' % m] = res[m]
     # the roll-outs alone (phase brackets inside gpmpc_rollout are per launch; time them as whole calls; K^-1 is there by now)
     t_roll = {}
     for m in ('ME', 'TA', 'EM'):
@@ -451,10 +463,11 @@ def run_b1(rk, h, N, d, calls=200):
                          'note': 'kernel = HIP events around the variance launch; whole call = crosscov + variance + finish launches back to back'}}
 
 
-def run_c4(rk, steps, warmup, N=4096, d=6, R=64, iters=4, verify_world1=True):
+def run_c4(rk, steps, warmup, N=4096, d=6, R=64, iters=4, verify_world1=True, dumped=None):
     """BASELINE config C4: log-marginal likelihood + gradient, R random restarts sharded over the ranks: restart r on
     rank r mod world inside gpmpc_train_multistart, ONE ncclAllGather of the (NLL, theta) table over an RCCL communicator
-    the library creates (on a CPU test box: the ranks' tables merged over gloo by gp_mpc_amd.train)."""
+    the library creates (on a CPU test box: the ranks' tables merged over gloo by gp_mpc_amd.train).
+    dumped: filled with the last timed step's gathered table and arg-min for --dump-outputs."""
     import hashlib
     import numpy as np
     from gp_mpc_amd._lib import Handle
@@ -482,6 +495,8 @@ def run_c4(rk, steps, warmup, N=4096, d=6, R=64, iters=4, verify_world1=True):
     if comm is not None:
         rk.lib.rccl_comm_destroy(comm)
     r = res['r']
+    if dumped is not None:
+        dumped.update(nll=r['obj'], theta=r['theta'], hyper=r['hyper'])
 
     def table_hash(rr):
         # the gathered (NLL, theta) table and the arg-min theta*, as bytes: equal hashes = bitwise equal tables
@@ -529,21 +544,50 @@ def run_c4(rk, steps, warmup, N=4096, d=6, R=64, iters=4, verify_world1=True):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, one `path/<name>.npy` each, float64
+    as computed.  Over DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of its rows (axis 0)."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES // total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def main():
     _own_stdout()
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
-    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--steps', type=int, default=None, help='timed steps (default: 20 for C2, 10 for C3, 5 for C4)')
+    ap.add_argument('--warmup', type=int, default=None, help='untimed steps before them (default: 3 for C2, 2 for C3, 1 for C4)')
     ap.add_argument('--N', type=int, default=4096)
     ap.add_argument('--d', type=int, default=6)
     ap.add_argument('--B', type=int, default=10000)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the C3 / C4 steps after the timed C2 region')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed C2 region, also measure everything beyond the headline figure: roofline and per-phase '
+                         'figures, the other step API, the CPU baseline and parity legs, B = 1 streaming, the C3 / C4 / C5 '
+                         'secondary configurations (world 1) or the restart shard (world > 1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path computed in its last step as DIR/<name>.npy (float64, <= 64 MB in all; '
+                         'bench_outputs/ is the folder git ignores)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and parity legs')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the B = 1 and C3 / C4 steps after the timed C2 region')
     ap.add_argument('--two-calls', action='store_true', help='C2 step as gpmpc_fit + gpmpc_predict_mean_var (r01-r05) instead of ONE gpmpc_fit_predict_mean_var call (same bits; the one call is 0.5-1 % faster: the host round trip between the calls is off the device path)')
     ap.add_argument('--restarts', type=int, default=64, help='restarts of the restart-shard leg (C4)')
     ap.add_argument('--config', default='C2', choices=['C2', 'C3', 'C4'])
     args = ap.parse_args()
+    steps0, warmup0 = {'C2': (20, 3), 'C3': (10, 2), 'C4': (5, 1)}[args.config]
+    args.steps = steps0 if args.steps is None else args.steps
+    args.warmup = warmup0 if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return _launch_ranks(args.gpus)
     import numpy as np
@@ -553,19 +597,24 @@ def main():
     rk = Ranks()
     rank, local_rank, world = rk.rank, rk.dev_index, rk.world
     lib = rk.lib
+    dumped = {}
     if args.config == 'C3':
-        out = run_c3(rk, min(args.steps, 10), min(args.warmup, 2), N=args.N if args.N != 4096 else 8192)
+        out = run_c3(rk, args.steps, args.warmup, N=args.N if args.N != 4096 else 8192, dumped=dumped)
     elif args.config == 'C4':
-        out = run_c4(rk, min(args.steps, 5), min(args.warmup, 1), N=args.N, d=args.d, R=args.restarts)
+        out = run_c4(rk, args.steps, args.warmup, N=args.N, d=args.d, R=args.restarts, dumped=dumped)
     if args.config != 'C2':
         rk.close()
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, dumped)
             _emit(out)
         return
 
     N, d, B = args.N, args.d, args.B
+    full = args.full
     p = synthetic_problem(N, d, 1, B, seed=1234 + rank, sn=1e-2)
-    layout, mfma_rate = lib.mfma_selftest(local_rank)
+    if full:
+        layout, mfma_rate = lib.mfma_selftest(local_rank)
     h = Handle(lib, p['X'], p['Y'], device=local_rank)
     dev = rk.device
     z = torch.from_numpy(p['Z']).to(dev)
@@ -586,10 +635,42 @@ def main():
 
     step = step_two_calls if two_calls else step_fused
 
-    # Timed region: only the dominant kernel is bracketed by events (the roofline needs its launch durations from THIS region);
-    # bracketing all seven phases costs 65 us per step (tools/bench_noprof.py), so the phase split comes from a second,
-    # untimed pass with all brackets on.
-    elapsed, prof_timed = timed(rk, h, step, args.steps, args.warmup, phases=('vargemm',))
+    if not full:
+        # the headline alone: no event brackets in the timed region
+        elapsed, _ = timed(rk, h, step, args.steps, args.warmup, profile=False)
+    else:
+        # Timed region: only the dominant kernel is bracketed by events (the roofline needs its launch durations from THIS region);
+        # bracketing all seven phases costs 65 us per step (tools/bench_noprof.py), so the phase split comes from a second,
+        # untimed pass with all brackets on.
+        elapsed, prof_timed = timed(rk, h, step, args.steps, args.warmup, phases=('vargemm',))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'mean': mean.cpu().numpy(), 'var': var.cpu().numpy()})
+    out = None
+    if rank == 0:
+        out = {
+            'metric': 'GP predict (mean+var)/sec, N=4096 d=6 fp64', 'value': world * B * args.steps / elapsed, 'unit': 'predictions/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3,
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+            'config': {'workload': 'C2: single-output SE-ARD GP, K build + Cholesky + 10k mean+var predictions per step',
+                       'N': N, 'd': d, 'Ny': 1, 'B': B, 'parallelism': f'independent GP per GPU x{world}'},
+            'step_api': 'gpmpc_fit + gpmpc_predict_mean_var' if two_calls else 'gpmpc_fit_predict_mean_var (one call; bitwise the two calls)',
+            'fused_fit_predicts': int(h.counter('fused_fit_predicts')),
+            'runtime': lib.runtime_info(),
+            'device': lib.device_name(local_rank),
+            # the persistent chain / worker kernels assume co-residency; a hand-off that times out falls back to the
+            # single-queue factorisation (correct, slower): on a shared GPU this count says the fast path degraded
+            'handoff_timeouts': int(h.counter('handoff_timeouts')),
+            'chained_factorisations': int(h.counter('chained_factorisations')),
+            'single_queue_factorisations': int(h.counter('single_queue_factorisations')),
+        }
+    if not full:
+        h.close()
+        del z, mean, var
+        rk.close()
+        if rank == 0:
+            _emit(out)
+        return
+
     phase_steps = max(5, min(args.steps, 20))
     elapsed_all, prof = timed(rk, h, step, phase_steps, 0)
     prof = {k: (v[0] * args.steps / phase_steps, v[1] * args.steps / phase_steps) for k, v in prof.items()}   # as if over `steps` steps (launch counts scaled, not rounded)
@@ -611,32 +692,22 @@ def main():
                 traffic_source = 'profiles/traffic.json (' + str(tj.get('source', 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, committed')) + ')'
         except Exception:
             traffic = None
-    out = None
     if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        value = world * B * args.steps / elapsed
         gemm_ms, gemm_n = prof['vargemm']
         flops = float(N) * (N + 1) * B              # 2 * N(N+1)/2 MACs per prediction (triangular L^-1)
         achieved = flops / (gemm_ms / max(gemm_n, 1) * 1e-3) * 1e-12 if gemm_ms > 0 else 0.0
         fac_ms, fac_n = prof['factor']
-        out = {
-            'metric': 'GP predict (mean+var)/sec, N=4096 d=6 fp64', 'value': value, 'unit': 'predictions/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'config': {'workload': 'C2: single-output SE-ARD GP, K build + Cholesky + 10k mean+var predictions per step',
-                       'N': N, 'd': d, 'Ny': 1, 'B': B, 'parallelism': f'independent GP per GPU x{world}'},
+        out.update({
             'roofline': {'kernel': 'vargemm_persist_kernel: 128x128 tiles over a static schedule, 512 resident workgroups (variance GEMM + column sum of squares)',
                          'bound': 'mfma', 'achieved': achieved, 'peak': FP64_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
                          'frac': achieved / FP64_MFMA_PEAK_TFLOPS, 'traffic': traffic, 'traffic_source': traffic_source,
                          'avg_launch_ms': gemm_ms / max(gemm_n, 1), 'launches': gemm_n,
                          'peak_measured_mfma_only_ubench': mfma_rate},
-            'step_api': 'gpmpc_fit + gpmpc_predict_mean_var' if two_calls else 'gpmpc_fit_predict_mean_var (one call; bitwise the two calls)',
             'ms_per_step_other_api': {'api': 'gpmpc_fit_predict_mean_var' if two_calls else 'gpmpc_fit + gpmpc_predict_mean_var',
                                       'ms_per_step': elapsed_other / 10 * 1e3, 'steps': 10},
             'fused_fit_predicts': int(h.counter('fused_fit_predicts')),
             'phases_ms_per_step': {k: v[0] / args.steps for k, v in prof.items() if v[1] > 0},
             'ms_per_step_all_brackets': elapsed_all / phase_steps * 1e3,   # the second pass: every phase bracketed, as r01-r03's lines were timed
-            'runtime': lib.runtime_info(),
             'phases_source': 'second, untimed pass of %d steps with every phase bracketed by events (all brackets on cost ~65 us per step); vargemm and the roofline: from the timed region, the only bracket there' % phase_steps,
             'cholesky': (lambda ms, n: {'kernel': 'chol_chain_kernel (+ chol_worker_kernel x3, concurrent)', 'bound': 'mfma',
                                         'achieved': (N ** 3 / 3.0) / (ms / max(n, 1) * 1e-3) * 1e-12 if ms > 0 else 0.0,
@@ -648,13 +719,12 @@ def main():
                                       'tflops': (2.0 * N ** 3 / 3.0) / (fac_ms / max(fac_n, 1) * 1e-3) * 1e-12 if fac_ms > 0 else 0.0,
                                       'note': 'N^3/3 (potrf) + N^3/3 (trtri) flops: blocked right-looking Cholesky + level-batched inverse'},
             'predict_only_per_s': B / max((prof['crosscov'][0] + prof['vargemm'][0] + prof['finish'][0]) / args.steps * 1e-3, 1e-12),
-            'device': lib.device_name(local_rank), 'mfma_layout': layout,
-            # the persistent chain / worker kernels assume co-residency; a hand-off that times out falls back to the
-            # single-queue factorisation (correct, slower): on a shared GPU this count says the fast path degraded
+            'mfma_layout': layout,
+            # (the counters again, now over the extra passes too)
             'handoff_timeouts': int(h.counter('handoff_timeouts')),
             'chained_factorisations': int(h.counter('chained_factorisations')),
             'single_queue_factorisations': int(h.counter('single_queue_factorisations')),
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             cb, cmean, cvar, mscale = cpu_baseline(p, B)
             out['cpu_baseline'] = cb

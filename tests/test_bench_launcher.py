@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -29,7 +30,7 @@ def run_bench(*flags, env=None, timeout=900):
 def test_gpus_2_launches_two_ranks_and_reports_the_restart_shard():
     subprocess.check_call([os.path.join(HERE, 'emu', 'build_emu.sh')], stdout=subprocess.DEVNULL)
     j = run_bench('--gpus', '2', '--N', '128', '--B', '64', '--steps', '2', '--warmup', '1', '--restarts', '4',
-                  '--no-cpu-baseline')
+                  '--full', '--no-cpu-baseline')
     assert j['n_gpus'] == 2 and j['steps'] == 2 and j['scaling'] == 'weak'
     assert j['config']['N'] == 128 and j['value'] > 0
     rs = j['restart_shard']
@@ -60,3 +61,40 @@ def test_config_c4_under_an_external_launcher_env():
     assert outs[1][0].strip() == ''                                              # only rank 0 prints
     j = json.loads(outs[0][0].strip())
     assert j['n_gpus'] == 2 and j['scaling'] == 'strong' and j['finite_restarts'] == 4
+
+
+@pytest.mark.timeout(1200)
+def test_plain_run_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run is the headline alone (the rest is --full's), times exactly --steps steps after --warmup, and
+    --dump-outputs writes the last timed step's mean / variance: the same bits from run to run and with --full."""
+    subprocess.check_call([os.path.join(HERE, 'emu', 'build_emu.sh')], stdout=subprocess.DEVNULL)
+    dumps = []
+    for k, (steps, warmup) in enumerate(((3, 1), (1, 0))):
+        j = run_bench('--N', '128', '--B', '64', '--steps', str(steps), '--warmup', str(warmup), '--dump-outputs', str(tmp_path / str(k)))
+        assert j['n_gpus'] == 1 and j['steps'] == steps and j['warmup'] == warmup
+        assert j['unit'] == 'predictions/s' and j['higher_is_better'] is True and j['dtype'] == 'f64'
+        assert j['ms_per_step'] > 0 and abs(j['value'] - 64 * 1e3 / j['ms_per_step']) <= 1e-6 * j['value']
+        assert j['chained_factorisations'] + j['single_queue_factorisations'] == steps + warmup     # one fit per step
+        assert not {'roofline', 'cholesky', 'phases_ms_per_step', 'ms_per_step_other_api', 'cpu_baseline', 'secondary'} & set(j)
+        dumps.append({n: np.load(tmp_path / str(k) / f'{n}.npy') for n in ('mean', 'var')})
+    j = run_bench('--N', '128', '--B', '64', '--steps', '2', '--warmup', '1', '--full', '--no-secondary',
+                  '--dump-outputs', str(tmp_path / 'full'))
+    assert {'roofline', 'cholesky', 'phases_ms_per_step', 'ms_per_step_other_api', 'cpu_baseline', 'parity_vs_oracle'} <= set(j)
+    assert j['parity_vs_oracle']['mean_rel_to_max'] <= 1e-10
+    dumps.append({n: np.load(tmp_path / 'full' / f'{n}.npy') for n in ('mean', 'var')})
+    for n in ('mean', 'var'):
+        assert dumps[0][n].shape == (64, 1) and dumps[0][n].dtype == np.float64 and np.all(np.isfinite(dumps[0][n]))
+        assert all(np.array_equal(dumps[0][n], d[n]) for d in dumps[1:])
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_limit(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 8 * 1000)
+    a, b = np.arange(2000.0).reshape(1000, 2), np.arange(1000, dtype=np.float32)
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), {'a': a, 'b': b})
+    sa, sb = np.load(tmp_path / '0' / 'a.npy'), np.load(tmp_path / '0' / 'b.npy')
+    assert sa.dtype == sb.dtype == np.float64 and sa.nbytes + sb.nbytes <= 8 * 1000 and len(sa) == len(sb) > 0
+    assert np.array_equal(sa[:, 0] / 2, sb) and np.all(np.diff(sb) > 0)              # the same rows of both, in order
+    assert np.array_equal(sa, np.load(tmp_path / '1' / 'a.npy')) and np.array_equal(sb, np.load(tmp_path / '1' / 'b.npy'))

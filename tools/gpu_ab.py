@@ -7,7 +7,7 @@ VARIANT = label[:KEY=VAL[,KEY=VAL...]] -- environment switches of the library (I
 variant; the pseudo key `lib=<name>` copies tools/ab_libs/<name>.so over the product library for the variant's runs (built here
 from another commit: `tools/build_ab_lib.sh <commit> <name>`; the .so files travel with gpurun, git ignores them).
 The variants run interleaved, `--rounds` times each, on whatever box the call landed on; every run is the JSON line of
-`--cmd` (default: the C2 bench without CPU baseline / secondary configs); `--fields` are dotted paths into that line.
+`--cmd` (default: the C2 bench with --full, without CPU baseline / secondary configs); `--fields` are dotted paths into that line.
 Prints one row per run and the per-variant mean / min; writes the same text to --out (under gpurun_out/)."""
 import argparse
 import json
@@ -31,7 +31,7 @@ def dig(j, path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=3)
-    ap.add_argument('--cmd', default='python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-secondary')
+    ap.add_argument('--cmd', default='python bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-secondary')
     ap.add_argument('--fields', default='ms_per_step,phases_ms_per_step.chain,phases_ms_per_step.factor,'
                                         'phases_ms_per_step.crosscov,phases_ms_per_step.vargemm')
     ap.add_argument('--out', default=None)

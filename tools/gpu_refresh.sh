@@ -16,7 +16,7 @@ if has tests; then
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
 fi
 if has bench; then
-  timeout 600 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; python - "$O/${TAG}_bench.json" <<'PY'
+  timeout 600 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; python - "$O/${TAG}_bench.json" <<'PY'
 import json, sys
 j = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])
 print('C2 value %.0f ms/step %.3f (all brackets %.3f) vargemm frac %.3f cholesky frac %.3f phases %s' % (j['value'], j['ms_per_step'], j['ms_per_step_all_brackets'], j['roofline']['frac'], j['cholesky']['frac'], {k: round(v, 3) for k, v in j['phases_ms_per_step'].items()}))
@@ -28,7 +28,7 @@ PY
 fi
 if has trace; then
   cd /tmp
-  timeout 600 rocprofv3 --kernel-trace --stats -d "$O/prof_$TAG" -o t -- python "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-secondary > "$O/prof_$TAG.log" 2>&1; echo "rocprof C2 rc=$?"
+  timeout 600 rocprofv3 --kernel-trace --stats -d "$O/prof_$TAG" -o t -- python "$R/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline --no-secondary > "$O/prof_$TAG.log" 2>&1; echo "rocprof C2 rc=$?"
   python "$R/tools/prof_summary.py" "$O/prof_$TAG/t_results.db" --steps 6 > "$O/${TAG}_kernel_trace_bench.txt"; head -12 "$O/${TAG}_kernel_trace_bench.txt"
   python "$R/tools/step_timeline.py" "$O/prof_$TAG/t_results.db" > "$O/${TAG}_step_timeline.txt" 2>&1; rm -rf "$O/prof_$TAG"
   timeout 600 rocprofv3 --kernel-trace --stats -d "$O/prof_${TAG}c3" -o t -- python "$R/bench.py" --config C3 --steps 2 --warmup 1 > "$O/prof_${TAG}c3.log" 2>&1; echo "rocprof C3 rc=$?"
@@ -36,7 +36,7 @@ if has trace; then
   timeout 600 rocprofv3 --kernel-trace --stats -d "$O/prof_${TAG}c4" -o t -- python "$R/bench.py" --config C4 --steps 1 --warmup 1 > "$O/prof_${TAG}c4.log" 2>&1; echo "rocprof C4 rc=$?"
   python "$R/tools/prof_summary.py" "$O/prof_${TAG}c4/t_results.db" --steps 2 > "$O/${TAG}_kernel_trace_bench_c4.txt"; head -8 "$O/${TAG}_kernel_trace_bench_c4.txt"; rm -rf "$O/prof_${TAG}c4"
   cd "$R"
-  GPMPC_CHAIN_TRACE=$O/ct_$TAG.bin timeout 120 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > /dev/null 2>&1
+  GPMPC_CHAIN_TRACE=$O/ct_$TAG.bin timeout 120 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > /dev/null 2>&1
   python tools/chain_trace.py $O/ct_$TAG.bin 64 > $O/${TAG}_chain_trace.txt 2>&1; head -13 $O/${TAG}_chain_trace.txt | tail -5
   python tools/worker_trace.py $O/ct_$TAG.bin 64 2>&1 | grep -v "^ *[0-9]*a .*-7[0-9][0-9][0-9][0-9][0-9][0-9]" > $O/${TAG}_worker_trace.txt; rm -f $O/ct_$TAG.bin
 fi
@@ -44,7 +44,7 @@ if has pmc; then
   cd /tmp
   for C in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVES SQ_INSTS_VALU_MFMA_MOPS_F64"; do
     N=$(echo $C | tr ' ' '_' | cut -c1-24)
-    timeout 600 rocprofv3 --kernel-trace --pmc $C -d "$O/pmc_${TAG}_$N" -o p -- python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > "$O/pmc_${TAG}_$N.log" 2>&1
+    timeout 600 rocprofv3 --kernel-trace --pmc $C -d "$O/pmc_${TAG}_$N" -o p -- python "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > "$O/pmc_${TAG}_$N.log" 2>&1
     echo "== $C rc=$?"
     python "$R/tools/pmc_summary.py" "$O/pmc_${TAG}_$N/p_results.db" > "$O/${TAG}_pmc_$N.txt" 2>&1; grep -A4 "vargemm_persist" "$O/${TAG}_pmc_$N.txt" | head -6
   done
@@ -70,7 +70,7 @@ PY
   cd "$R"
 fi
 if has soak; then
-  timeout 300 python bench.py --steps 1000 --warmup 3 --no-cpu-baseline --no-secondary 2>$O/soak_err.log | python -c "
+  timeout 300 python bench.py --full --steps 1000 --warmup 3 --no-cpu-baseline --no-secondary 2>$O/soak_err.log | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('soak 1000 steps: value %8.0f  ms/step %.3f  factor %.3f vargemm %.3f  handoff_timeouts %s' % (d['value'], d['ms_per_step'], d['phases_ms_per_step']['factor'], d['phases_ms_per_step']['vargemm'], d.get('handoff_timeouts')))" | tee $O/${TAG}_soak.txt
   echo "time-out messages: $(grep -c 'timed out' $O/soak_err.log)" | tee -a $O/${TAG}_soak.txt

@@ -40,6 +40,6 @@ out = {
     'algorithmic_bytes': 4 * N * (N + 1) + 8 * N * B,      # lower triangle of L^-1 + the cross-covariances, read once
     'matrix_pipe_busy': mf / (4.0 * cu) if cu else None,
     'source': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES (separate passes) '
-              '-- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary; tools/gpu_refresh.sh %s pmc' % (sys.argv[4] if len(sys.argv) > 4 else ''),
+              '-- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary; tools/gpu_refresh.sh %s pmc' % (sys.argv[4] if len(sys.argv) > 4 else ''),
 }
 print(json.dumps(out, indent=1))
