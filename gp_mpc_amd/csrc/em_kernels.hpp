@@ -478,7 +478,8 @@ em_diag_kernel(const double* __restrict__ ops, const double* __restrict__ beta, 
     const double* __restrict__ Lb = o + (long)(2 * EMK + 1) * Np;
     const double* __restrict__ ba = beta + (long)a * Np;
     // K^-1: accumulator register r of a lane sits crow-step rows below register 0 -- four wave-uniform row bases and ONE
-    // 32-bit element offset per lane (host: Np^2 < 2^29), which the compiler turns into scalar-base loads
+    // 32-bit element offset per lane, which the compiler turns into scalar-base loads (it would wrap from Np^2 >= 2^32 on:
+    // predict_moments_chunk sends such sizes to em_pair2_kernel<true> instead)
     const long cstep = (long)(crow(0, 1, crow_mode) - crow(0, 0, crow_mode)) * Np;
     const double* __restrict__ iK0 = invK + (long)a * Np * Np;
     const double* __restrict__ iK1 = iK0 + cstep;

@@ -56,7 +56,10 @@ static int predict_moments_chunk(gpmpc_gp* h, int method, int B, const double* d
         static const int diag_segs_env = getenv("GPMPC_EM_DIAG_SEGS") ? atoi(getenv("GPMPC_EM_DIAG_SEGS")) : -1;
         const long tri = (long)tiles * (tiles + 1) / 2;
         const int diag_want = g_em_diag_segs >= 0 ? g_em_diag_segs : diag_segs_env >= 0 ? diag_segs_env : em_diag_default_segs(g_cu_count[h->device], Ny, tri);
-        const int diag_segs = (int)std::min<long>(std::min(diag_want, 4096), tri);
+        // (em_diag_kernel addresses K^-1 by a 32-bit element offset: from Np^2 >= 2^32 on -- 34 GB per K^-1 -- the a == b pairs
+        //  take strips and chunks, whose kernel uses 64-bit offsets)
+        const bool ko32 = (long)Np * Np < (1L << 32);
+        const int diag_segs = ko32 ? (int)std::min<long>(std::min(diag_want, 4096), tri) : 0;
         const int nslots = std::max(nstrip, diag_segs);
         const long prepN = (long)B * (Ny + P) * (d * d + 1), partN = (long)B * P * nslots;
         const long opsN = (long)B * P * (2 * KD + 2) * Np, mpartN = (long)B * Ny * EM_MEAN_CHUNKS, bndN = (long)B * P * 4;

@@ -13,6 +13,7 @@ Tolerances: fp64 throughout.
   NLL:  |dNLL| / (|NLL| + N) <= 1e-10 on well-conditioned data
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -615,6 +616,8 @@ def check_em_chunks(lib, N=300, d=3, Ny=2, seed=12):
                 ref = c
             else:
                 assert np.max(np.abs(c - ref)) <= 1e-12 * max(1.0, np.abs(ref).max()) * 1e3, (chunk, segs)
+        check_em_fixed_input(lib, f'chunks N={N} d={d}', X, Y, H, Z, S, h=h, tunings=[
+            (f'chunk {chunk} segs {segs}', chunk, segs) for chunk, segs in ((1, 0), (3, 0), (1000, 0), (1000, 1), (2, 4), (1, -1), (1000, 12))])
     finally:
         lib.set_tuning('em_chunk', 0)
         lib.set_tuning('em_diag_segs', -1)
@@ -1416,6 +1419,36 @@ def check_rollout_vs_oracle(lib, N, Ny, d, T, seed=77, uscale=0.3):
     gp.close()
 
 
+def _solve_ld(A, B):
+    """Small (Nx x Nx) systems A^-1 B: Gauss-Jordan with partial pivoting in longdouble (TEST ONLY)."""
+    A, B = A.copy(), B.copy()
+    n = len(A)
+    for i in range(n):
+        piv = i + int(np.argmax(np.abs(A[i:, i])))
+        A[[i, piv]], B[[i, piv]] = A[[piv, i]], B[[piv, i]]
+        B[i] = B[i] / A[i, i]
+        A[i] = A[i] / A[i, i]
+        for r in range(n):
+            if r != i:
+                B[r] = B[r] - A[r, i] * B[i]
+                A[r] = A[r] - A[r, i] * A[i]
+    return B
+
+
+def _det_ld(A):
+    """|det A| of a small matrix by elimination with partial pivoting in longdouble (TEST ONLY)."""
+    A = A.copy()
+    n, det = len(A), np.longdouble(1)
+    for i in range(n):
+        piv = i + int(np.argmax(np.abs(A[i:, i])))
+        if piv != i:
+            A[[i, piv]] = A[[piv, i]]
+            det = -det
+        det = det * A[i, i]
+        A[i + 1:] = A[i + 1:] - np.outer(A[i + 1:, i] / A[i, i], A[i])
+    return abs(det)
+
+
 def exact_moment_longdouble(X, Y, H, mu, Sigma):
     """gp_exact_moment (gp_functions.py:344-418) evaluated in longdouble (TEST ONLY: the yardstick for how far an fp64
     evaluation -- the oracle's, the device's -- is from the formula's exact value): K^-1 column by column is too much at
@@ -1431,32 +1464,6 @@ def exact_moment_longdouble(X, Y, H, mu, Sigma):
     v = X.astype(ld) - mu
     eye = np.eye(Nx, dtype=ld)
 
-    def solve_ld(A, B):                                  # small (Nx x Nx) systems: Gauss-Jordan in longdouble
-        A, B = A.copy(), B.copy()
-        n = len(A)
-        for i in range(n):
-            piv = i + int(np.argmax(np.abs(A[i:, i])))
-            A[[i, piv]], B[[i, piv]] = A[[piv, i]], B[[piv, i]]
-            B[i] = B[i] / A[i, i]
-            A[i] = A[i] / A[i, i]
-            for r in range(n):
-                if r != i:
-                    B[r] = B[r] - A[r, i] * B[i]
-                    A[r] = A[r] - A[r, i] * A[i]
-        return B
-
-    def det_ld(A):
-        A = A.copy()
-        n, det = len(A), ld(1)
-        for i in range(n):
-            piv = i + int(np.argmax(np.abs(A[i:, i])))
-            if piv != i:
-                A[[i, piv]] = A[[piv, i]]
-                det = -det
-            det = det * A[i, i]
-            A[i + 1:] = A[i + 1:] - np.outer(A[i + 1:, i] / A[i, i], A[i])
-        return abs(det)
-
     beta, Kl, cfs = [], [], []
     for a in range(Ny):
         al, K = longdouble_alpha(X, Y[:, a], H[a])
@@ -1468,9 +1475,9 @@ def exact_moment_longdouble(X, Y, H, mu, Sigma):
     for a in range(Ny):
         iLam = np.diag(np.exp(-2 * Hl[a, :Nx]))
         R = S + np.diag(np.exp(2 * Hl[a, :Nx]))
-        iR = iLam @ (eye - solve_ld(eye + S @ iLam, S @ iLam))
+        iR = iLam @ (eye - _solve_ld(eye + S @ iLam, S @ iLam))
         T = v @ iR
-        c = np.exp(2 * Hl[a, Nx]) / np.sqrt(det_ld(R)) * np.exp(np.sum(Hl[a, :Nx]))
+        c = np.exp(2 * Hl[a, Nx]) / np.sqrt(_det_ld(R)) * np.exp(np.sum(Hl[a, :Nx]))
         mean[a] = np.sum(c * np.exp(-np.sum(T * v, axis=1) * ld(0.5)) * beta[a])
         v1 = v / np.exp(Hl[a, :Nx])[None, :]
         log_k[:, a] = 2 * Hl[a, Nx] - np.sum(v1 * v1, axis=1) * ld(0.5)
@@ -1479,9 +1486,9 @@ def exact_moment_longdouble(X, Y, H, mu, Sigma):
         ii = v / np.exp(2 * Hl[a, :Nx])[None, :]
         for b in range(a + 1):
             R = S @ np.diag(np.exp(-2 * Hl[a, :Nx]) + np.exp(-2 * Hl[b, :Nx])) + eye
-            t = 1 / np.sqrt(det_ld(R))
+            t = 1 / np.sqrt(_det_ld(R))
             ij = v / np.exp(2 * Hl[b, :Nx])[None, :]
-            Q1 = solve_ld(R, S * ld(0.5))
+            Q1 = _solve_ld(R, S * ld(0.5))
             aQ, bQ = ii @ Q1, (-ij) @ Q1
             maha = np.sum(aQ * ii, axis=1)[:, None] + np.sum(bQ * (-ij), axis=1)[None, :] - 2 * aQ @ (-ij).T
             Q = np.exp(log_k[:, a][:, None] + log_k[:, b][None, :] + maha)
@@ -1495,6 +1502,226 @@ def exact_moment_longdouble(X, Y, H, mu, Sigma):
         cov[a, a] += np.exp(2 * Hl[a, Nx])
     cov = cov - np.outer(mean, mean)
     return mean.astype(np.float64), cov.astype(np.float64)
+
+
+def _ld_words(s):
+    """Longdouble values as fp64 words, exactly: s == hi + lo (a 64-bit significand less its 53-bit rounding fits in 11 bits)."""
+    s = np.asarray(s, dtype=np.longdouble).ravel()
+    hi = s.astype(np.float64)
+    return list(hi) + list((s - hi.astype(np.longdouble)).astype(np.float64))
+
+
+def _fsum_ld(words):
+    """The exact sum of fp64 words, rounded to longdouble: fsum's correctly rounded sum plus fsum of what it left over."""
+    hi = math.fsum(words)
+    return np.longdouble(hi) + np.longdouble(math.fsum(words + [-hi]))
+
+
+def em_fixed_input_longdouble(invK, X, Y, H, mu, Sigma, rows=(256, 173)):
+    """gp_exact_moment (gp_functions.py:344-418) of FIXED fp64 inputs -- K^-1 as given (the device's own), X, Y, hyper, mu,
+    Sigma -- evaluated in longdouble (TEST ONLY): the yardstick of the pair-sum kernels alone.  beta = K^-1 y is formed in
+    longdouble from that same K^-1; no N^3 step, O(N^2 d) per output pair in row blocks (memory stays bounded at N = 8192).
+    Every block's partial sum is split into two fp64 words and the words are added exactly (math.fsum).
+    The whole evaluation is done TWICE, independently: row blocks of rows[0] over (i, j) with maha's cross term as
+    (2 ii_i S') . ij_j, and row blocks of rows[1] over the transposed (j, i) with the cross term as ii_i . (2 ij_j S'^T); the
+    mean once as one pairwise sum with (Sigma + Lambda)^-1 from the identity the reference uses, once as block words with
+    the inverse solved directly.  Returns dict(mean, cov, mean2, cov2) as longdouble -- the spread between the two is the
+    yardstick's own error (check_em_fixed_input certifies it) -- and the 2-norms of the summands, mean_l2 = ||beta_a q_a||
+    and cov_l2 = t ||A o Q|| per pair: one fp64 rounding of every summand moves a sum by about eps times that norm (a
+    random walk), whatever the order it is added in.  invK: sequence of Ny [N, N] matrices."""
+    ld = np.longdouble
+    Ny, (N, d) = len(H), X.shape
+    Hl = np.asarray(H, dtype=np.float64).astype(ld)
+    v = X.astype(ld) - np.asarray(mu, dtype=np.float64).astype(ld).reshape(1, d)
+    S = np.asarray(Sigma, dtype=np.float64).astype(ld)
+    eye = np.eye(d, dtype=ld)
+    ell2 = Hl[:, :d] ** 2
+    sf2 = Hl[:, d] ** 2
+    beta = []
+    for a in range(Ny):
+        y = Y[:, a].astype(ld)
+        beta.append(np.concatenate([np.sum(invK[a][r0:r0 + 256].astype(ld) * y[None, :], axis=1) for r0 in range(0, N, 256)]))
+    log_k = [np.log(sf2[a]) - ld(0.5) * np.sum(v * v / ell2[a][None, :], axis=1) for a in range(Ny)]
+    means, mean_l2 = [], np.zeros(Ny)
+    for form in (0, 1):
+        m = np.zeros(Ny, dtype=ld)
+        for a in range(Ny):
+            R = S + np.diag(ell2[a])
+            if form == 0:
+                iLam = np.diag(1 / ell2[a])
+                iR = iLam @ (eye - _solve_ld(eye + S @ iLam, S @ iLam))
+            else:
+                iR = _solve_ld(R, eye)
+            c = sf2[a] / np.sqrt(_det_ld(R)) * np.prod(Hl[a, :d])
+            w = c * np.exp(-ld(0.5) * np.sum((v @ iR) * v, axis=1)) * beta[a]
+            mean_l2[a] = float(np.sqrt(np.sum(w * w)))
+            m[a] = np.sum(w) if form == 0 else _fsum_ld(sum((_ld_words(np.sum(w[r0:r0 + 97])) for r0 in range(0, N, 97)), []))
+        means.append(m)
+    covs, cov_l2 = [], np.zeros((Ny, Ny))
+    for form, bs in enumerate(rows):
+        cov = np.zeros((Ny, Ny), dtype=ld)
+        for a in range(Ny):
+            for b in range(a + 1):
+                R = S * (1 / ell2[a] + 1 / ell2[b])[None, :] + eye
+                t = 1 / np.sqrt(_det_ld(R))
+                Q1 = _solve_ld(R, S * ld(0.5))
+                ii, ij = v / ell2[a][None, :], v / ell2[b][None, :]
+                ra = log_k[a] + np.sum((ii @ Q1) * ii, axis=1)
+                rb = log_k[b] + np.sum((ij @ Q1) * ij, axis=1)
+                if form == 0:                    # row index i (output a), column index j (output b)
+                    rw, cw = (ra, 2 * (ii @ Q1), beta[a]), (rb, ij, beta[b])
+                else:                            # row index j, column index i
+                    rw, cw = (rb, 2 * (ij @ Q1.T), beta[b]), (ra, ii, beta[a])
+                words, sq = [], ld(0)
+                for r0 in range(0, N, bs):
+                    r1 = min(N, r0 + bs)
+                    E = rw[0][r0:r1, None] + cw[0][None, :]
+                    for k in range(d):
+                        E += rw[1][r0:r1, k:k + 1] * cw[1][:, k][None, :]
+                    A = rw[2][r0:r1, None] * cw[2][None, :]
+                    if a == b:
+                        A -= (invK[a][r0:r1] if form == 0 else invK[a][:, r0:r1].T).astype(ld)
+                    W = A * np.exp(E)
+                    words += _ld_words(np.sum(W))
+                    sq += np.sum(W * W)
+                cov[a, b] = cov[b, a] = t * _fsum_ld(words)
+                cov_l2[a, b] = cov_l2[b, a] = float(t * np.sqrt(sq))
+            cov[a, a] += sf2[a]
+        covs.append(cov - np.outer(means[form], means[form]))
+    return dict(mean=means[0], cov=covs[0], mean2=means[1], cov2=covs[1], mean_l2=mean_l2, cov_l2=cov_l2)
+
+
+# The device's distance from the fixed-input value, per output pair, against numpy's on the same inputs -- where numpy's is
+# taken as at least eps ||summands||, the size of one rounding of every summand (the summands cancel up to 13 digits deep,
+# and one fp64 evaluation lands at a random-walk distance of that size; profiles/em_fixed_input_error_scale.txt).  Not 2:
+# numpy against ITSELF, the same sums over the training points in another order, is more than 2 x numpy in 31 % of the
+# pairs (up to 15 x) and, with the eps ||summands|| floor, up to 2.3 x; the device's error is a median 0.83 and up to
+# 4.5 eps ||summands|| on the emulator against numpy's 0.64 and 2.4 (3.2 in the other order); per pair up to 7.0 x E_np on
+# the MI355X (profiles/em_fixed_input_digits.txt; the inputs are seeded and the sums run in a fixed order).  A tile
+# dropped or counted twice, or a wrong clamp route, is off by many orders of magnitude more.
+EM_GATE_RATIO = 8.0
+EM_GATE_FLOOR = 1e-13        # ... plus this much of max(|value|, sf^2)
+EM_YARDSTICK_SHARE = 0.05    # the yardstick's two evaluations may differ by this share of what it judges
+
+
+def _longdouble_or_skip():
+    if np.finfo(np.longdouble).nmant < 63:
+        import pytest
+        pytest.skip(f'longdouble has {np.finfo(np.longdouble).nmant} mantissa bits here (x87 80-bit: 63): no yardstick')
+
+
+def em_fixed_input_gate(label, dev_mean, dev_cov, np_mean, np_cov, ref, sf2):
+    """The fixed-input gate of one (case, input), for every checked output pair (and every output's mean) on its own: with
+    ref the longdouble value, E_dev = |device - ref| and E_np = max(|numpy(fp64, same K^-1) - ref|, eps ||summands||)
+    (numpy's error, or the size of one rounding of every summand of that pair when numpy's own sum happens to land closer
+    -- one draw of a random walk is no yardstick), E_dev <= EM_GATE_RATIO E_np + 1e-13 max(|ref|, sf^2).  The yardstick
+    certifies itself first: its two evaluations may differ by at most 5 % of the larger of E_np and the floor, pair by
+    pair, else 'yardstick too coarse'.  Prints one digits line (maxima over the pairs, and the largest per-pair ratio);
+    returns (E_dev/|cov|, E_np/|cov|, largest per-pair ratio)."""
+    eps = np.finfo(np.float64).eps
+    out = {}
+    for what, dv, nv in (('cov', dev_cov, np_cov), ('mean', dev_mean, np_mean)):
+        rv, rv2 = ref[what], ref[what + '2']
+        keep = np.tril(np.ones(rv.shape, dtype=bool)) if what == 'cov' else np.ones(rv.shape, dtype=bool)
+        e_dev = np.abs(np.asarray(dv, dtype=np.float64).astype(np.longdouble) - rv).astype(np.float64)[keep]
+        e_num = np.abs(np.asarray(nv, dtype=np.float64).astype(np.longdouble) - rv).astype(np.float64)[keep]
+        e_np = np.maximum(e_num, eps * np.asarray(ref[what + '_l2'], dtype=np.float64)[keep])
+        floor = EM_GATE_FLOOR * max(float(np.max(np.abs(rv))), float(np.max(sf2)))
+        spread = np.abs(rv - rv2).astype(np.float64)[keep]
+        assert np.all(spread <= EM_YARDSTICK_SHARE * np.maximum(e_np, floor)), ('yardstick too coarse', label, what, spread, e_np, floor)
+        ratio = float(np.max(e_dev / np.maximum(e_np, 1e-300)))
+        out[what] = (e_dev, e_np, floor, float(spread.max()), float(np.max(np.abs(rv))), float(e_num.max()), ratio)
+    (cd, cn, cf, cs, cmax, cnum, crat), (md, mn, mf, ms_, _, mnum, mrat) = out['cov'], out['mean']
+    print(f'[EM fixed input] {label}: max|cov| {cmax:.3e}  E_dev/|cov| {cd.max() / cmax:.2e}  E_np/|cov| {cn.max() / cmax:.2e} '
+          f'(numpy {cnum / cmax:.2e})  ratio per pair <= {crat:.2f}  yardstick spread/|cov| {cs / cmax:.1e};  '
+          f'mean: E_dev {md.max():.2e} E_np {mn.max():.2e} (numpy {mnum:.2e}) ratio <= {mrat:.2f} spread {ms_:.1e}')
+    assert np.all(cd <= EM_GATE_RATIO * cn + cf), ('EM covariance', label, cd, cn, cf)
+    assert np.all(md <= EM_GATE_RATIO * mn + mf), ('EM mean', label, md, mn, mf)
+    return float(cd.max() / cmax), float(cn.max() / cmax), crat
+
+
+def check_em_fixed_input(lib, label, X, Y, H, Z, S, tunings=(('default', 0, -1),), outs=None, h=None):
+    """The exact moments of the device against em_fixed_input_longdouble on the device's own K^-1, gated by
+    em_fixed_input_gate for every input of Z and every tuning (name, em_chunk, em_diag_segs; 0 / -1 = the defaults).
+    outs: the outputs whose pairs are checked (EM's pair (a, b) involves outputs a and b only).  h: a fitted handle (with
+    K^-1) to reuse.  Returns the (label, E_dev/|cov|, E_np/|cov|) of every check."""
+    _longdouble_or_skip()
+    own = h is None
+    if own:
+        h = Handle(lib, X, Y)
+        assert np.all(h.fit(H, want_invK=True) == 0), label
+    outs = list(range(len(H))) if outs is None else list(outs)
+    iK = h.get_factors(chol=False, alpha=False, invK=True)['invK']
+    iK = [iK[a].copy() for a in outs]
+    Yo, Ho = Y[:, outs], H[outs]
+    sf2 = Ho[:, X.shape[1]] ** 2
+    refs = [em_fixed_input_longdouble(iK, X, Yo, Ho, Z[b], S[b]) for b in range(len(Z))]
+    nps = [go.exact_moment(iK, X, Yo, Ho, Z[b], S[b]) for b in range(len(Z))]
+    res = []
+    try:
+        for name, chunk, segs in tunings:
+            lib.set_tuning('em_chunk', chunk)
+            lib.set_tuning('em_diag_segs', segs)
+            m, c = h.predict('EM', Z, S)
+            for b in range(len(Z)):
+                tag = f'{label} [{name}] input {b}'
+                res.append((tag,) + em_fixed_input_gate(tag, m[b][outs], c[b][np.ix_(outs, outs)], nps[b][0], nps[b][1], refs[b], sf2))
+    finally:
+        lib.set_tuning('em_chunk', 0)
+        lib.set_tuning('em_diag_segs', -1)
+        if own:
+            h.close()
+    return res
+
+
+def em_schedule_tunings(N):
+    """The a == b schedules around one pair's triangle of T tiles (em_diag_kernel): 1, 2 and 7 ranges, the default, T - 1,
+    T and more than T ranges; strips and chunks (em_diag_segs = 0) with 1, 3, 64 tiles per chunk and whole strips."""
+    tiles = -(-N // 64)
+    T = tiles * (tiles + 1) // 2
+    return ([(f'segs {s}', 0, s) for s in (1, 2, 7)] + [('default', 0, -1)] + [(f'segs {s}', 0, s) for s in (T - 1, T, T + 5)]
+            + [(f'chunk {c}, segs 0', c, 0) for c in (1, 3, 64, tiles)])
+
+
+def clustered_problem(N, d, Ny, B=1, M=11, seed=5, sn=0.1):
+    """A training set where every tile of the pair sums matters: M cluster centres within a length scale of the test
+    points, repeated with jitter in random order, so Q_ij = O(1) in every 64 x 64 tile -- a tile dropped or counted twice
+    moves the sum by O(1) of a tile's share."""
+    rng = np.random.default_rng(seed)
+    C = rng.uniform(-0.8, 0.8, (M, d))
+    X = C[rng.integers(0, M, N)] + 0.05 * rng.standard_normal((N, d))
+    Y = np.zeros((N, Ny))
+    for a in range(Ny):
+        y = np.sin(X @ rng.standard_normal(d)) + 0.1 * rng.standard_normal(N)
+        Y[:, a] = (y - y.mean()) / y.std()
+    H = np.hstack([np.full((Ny, d), 1.5) * (1 + 0.1 * np.arange(Ny))[:, None], np.ones((Ny, 1)), np.full((Ny, 1), sn)])
+    Z = 0.1 * rng.standard_normal((B, d))
+    A = rng.standard_normal((B, d, d))
+    S = np.einsum('bij,bkj->bik', A, A) * 5e-3 + 1e-2 * np.eye(d)
+    return X, Y, H, Z, S
+
+
+def check_em_fixed_input_clamp_routing(lib, N=300, d=3, seed=61):
+    """Clamp routing in one batch (em_needs_clamp, per input and pair): B = 3, Ny = 2 -- a near point, a point 1e5 length
+    scales away (every pair of that input clamps) and a third input near again; output 1 has length scales so small that
+    every pair that involves it takes the CLAMP instantiation at every input, the pair (0, 0) only at the far point.
+    Every input must give its own B = 1 call's bits, and the values must pass the fixed-input gate."""
+    p = go.synthetic_problem(N, d, 2, 3, seed=seed, sn=0.1)
+    X, Y, S = p['X'], p['Y'], p['Sigma'] * 30
+    H = p['hyper'].copy()
+    H[1, :d] = 1e-5
+    Z = p['Z'].copy()
+    Z[1] = Z[1] + 1e5 * H[0, :d]
+    h = Handle(lib, X, Y)
+    try:
+        assert np.all(h.fit(H, want_invK=True) == 0)
+        m, c = h.predict('EM', Z, S)
+        for b in range(len(Z)):
+            m1, c1 = h.predict('EM', Z[b:b + 1], S[b:b + 1])
+            assert np.array_equal(m1[0], m[b]) and np.array_equal(c1[0], c[b]), b
+        return check_em_fixed_input(lib, f'clamp routing N={N} d={d}', X, Y, H, Z, S, h=h)
+    finally:
+        h.close()
 
 
 def check_c3_size_step(h, p, outs=(1, 4), node=3):
@@ -1537,7 +1764,12 @@ def check_c3_size_step(h, p, outs=(1, 4), node=3):
     cmax = np.abs(ec).max()
     print(f'\n[C3 EM digits, N = {len(X)}] max|cov| {cmax:.3e}  cancellation scale / |cov| {scale.max() / cmax:.2e}  device vs oracle / |cov| '
           f'{np.abs(got - ec).max() / cmax:.2e} (gated at 1e-9 scale / |cov| = {bar / cmax:.2e})  min eig(cov): device {np.linalg.eigvalsh(got).min():.3e} oracle {np.linalg.eigvalsh(ec).min():.3e}')
-    return dict(ms=ms, bar_em=bar, em_scale_over_cov=float(scale.max() / cmax), em_dev_vs_oracle_over_cov=float(np.abs(got - ec).max() / cmax))
+    # beside that bar, the fixed-input gate (the device's own K^-1, its longdouble value): the default a == b schedule and
+    # strips and chunks (em_diag_segs = 0)
+    fx = check_em_fixed_input(h.lib, f'C3 N={len(X)} outputs {tuple(outs)} node {node}', X, p['Y'], H, z[None], S[None],
+                              tunings=(('default', 0, -1), ('strips and chunks', 0, 0)), outs=outs, h=h)
+    return dict(ms=ms, bar_em=bar, em_scale_over_cov=float(scale.max() / cmax), em_dev_vs_oracle_over_cov=float(np.abs(got - ec).max() / cmax),
+                fixed_input=fx)
 
 
 def check_em_against_extended_precision(lib, N=1024, d=8, Ny=2, seed=1234, sn=1e-2, nodes=(3, 7)):
@@ -1569,7 +1801,9 @@ def check_em_against_extended_precision(lib, N=1024, d=8, Ny=2, seed=1234, sn=1e
         # about the matrix MPC factors next)
         assert d_dev <= max(10.0 * d_orc, 1e-8 * cmax), (d_dev, d_orc, cmax)
         assert np.abs(m[0] - tm).max() <= max(2.0 * np.abs(om - tm).max(), 1e-10 * max(1.0, np.abs(tm).max()))
-        out.append((float(d_dev / cmax), float(d_orc / cmax)))
+        # the same covariance on FIXED inputs (the device's K^-1): what of the gap above the pair sums account for
+        fx = check_em_fixed_input(lib, f'N={N} d={d} Ny={Ny} node {node}', X, Y, H, z[None], S[None], h=h)
+        out.append((float(d_dev / cmax), float(d_orc / cmax), fx[0][1:]))
     h.close()
     return out
 
@@ -2460,6 +2694,7 @@ def check_random_shapes(lib, n_cases=10, seed=2024, nmax=220):
             sc = _em_scale(f['invK'], X, Y, H, Z[b], S[b]).max() + (H[:, d] ** 2).max()
             assert np.max(np.abs(me[b] - em)) <= 1e-9 * max(1.0, np.abs(em).max()), tag
             assert np.max(np.abs(ce[b] - ec)) <= 1e-9 * sc, tag
+        check_em_fixed_input(lib, f'random shape {tag}', X, Y, H, Z[:nb], S[:nb], h=h)
         a = int(rng.integers(0, Ny))
         v, g = h.nll(a, H[a], want_grad=True)
         ovv, og = go.nll_grad(H[a], X, Y[:, a])

@@ -347,3 +347,23 @@ def test_emu_far_points_and_zero_signal_variance(emu):
 def test_emu_gp_rollout_lockstep_route(emu):
     pc.check_gp_rollout_lockstep(emu)
     pc.check_gp_rollout_lockstep(emu, normalize=False, N=150)
+
+
+def test_emu_em_fixed_input_shapes(emu):
+    # the exact moments against the longdouble value of the device's own K^-1 (pc.em_fixed_input_gate): d = 1, the 8-deep
+    # cross term, the 16-deep one at d = 9 and d = 16, Ny = 1..3, ragged N
+    for N, d, Ny, B, seed in ((333, 1, 3, 2, 1), (577, 8, 2, 1, 2), (600, 9, 1, 2, 3), (421, 16, 3, 1, 4), (130, 8, 1, 1, 5)):
+        p = pc.go.synthetic_problem(N, d, Ny, B, seed=seed, sn=1e-2)
+        pc.check_em_fixed_input(emu, f'N={N} d={d} Ny={Ny}', p['X'], p['Y'], p['hyper'], p['Z'], p['Sigma'] * 30)
+
+
+def test_emu_em_fixed_input_schedules(emu):
+    # every tile matters (clustered training set): the a == b ranges and the strips-and-chunks split swept
+    X, Y, H, Z, S = pc.clustered_problem(555, 4, 2, B=2)
+    pc.check_em_fixed_input(emu, 'clustered N=555 d=4', X, Y, H, Z, S, tunings=pc.em_schedule_tunings(555))
+    X, Y, H, Z, S = pc.clustered_problem(390, 8, 3, B=1, seed=6)
+    pc.check_em_fixed_input(emu, 'clustered N=390 d=8 Ny=3', X, Y, H, Z, S, tunings=pc.em_schedule_tunings(390))
+
+
+def test_emu_em_fixed_input_clamp_routing(emu):
+    pc.check_em_fixed_input_clamp_routing(emu)

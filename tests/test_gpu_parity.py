@@ -408,3 +408,35 @@ def test_soak_chained_fits_without_a_handoff_timeout(lib):
 
 def test_gp_rollout_lockstep_route(lib):
     pc.check_gp_rollout_lockstep(lib, N=800, T=8)
+
+
+# ---- exact moments against the longdouble value of FIXED inputs (the device's own K^-1): pc.em_fixed_input_gate --------
+@pytest.mark.parametrize('N', [2048, 2049])
+def test_em_fixed_input_around_the_pair_overlap(lib, N):
+    """Ny = 2 at Np = 2048 (the a == b launch on the main queue) and Np = 2112 (on the aux queue next to the a != b launch,
+    last tile 1/64 live)."""
+    p = go.synthetic_problem(N, 8, 2, 1, seed=N, sn=1e-2)
+    pc.check_em_fixed_input(lib, f'N={N} d=8 Ny=2', p['X'], p['Y'], p['hyper'], p['Z'], p['Sigma'])
+
+
+def test_em_fixed_input_one_output(lib):
+    """Ny = 1 at N = 4100: no a != b launch, no overlap."""
+    p = go.synthetic_problem(4100, 8, 1, 1, seed=41, sn=1e-2)
+    pc.check_em_fixed_input(lib, 'N=4100 d=8 Ny=1', p['X'], p['Y'], p['hyper'], p['Z'], p['Sigma'])
+
+
+@pytest.mark.parametrize('d', [9, 16])
+def test_em_fixed_input_16_deep_cross_term(lib, d):
+    p = go.synthetic_problem(2500 + d, d, 2, 1, seed=d, sn=1e-2)
+    pc.check_em_fixed_input(lib, f'N={2500 + d} d={d} Ny=2', p['X'], p['Y'], p['hyper'], p['Z'], p['Sigma'] * 30)
+
+
+def test_em_fixed_input_schedules_where_every_tile_matters(lib):
+    """Clustered training set (Q = O(1) in every tile), N = 3001: the a == b ranges (1, 2, 7, default, T - 1, T, > T) and
+    strips and chunks (1, 3, 64 tiles, whole strips)."""
+    X, Y, H, Z, S = pc.clustered_problem(3001, 4, 2, B=1)
+    pc.check_em_fixed_input(lib, 'clustered N=3001 d=4 Ny=2', X, Y, H, Z, S, tunings=pc.em_schedule_tunings(3001))
+
+
+def test_em_fixed_input_clamp_routing(lib):
+    pc.check_em_fixed_input_clamp_routing(lib)
