@@ -64,6 +64,7 @@ SIGNATURES = {
     'gpmpc_rollout': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gpmpc_rollout_feedback': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gpmpc_rollout_multi': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gpmpc_rollout_multi_feedback': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int] + [_vp] * 12),
     'gpmpc_predict': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
     'gpmpc_covar': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     'gpmpc_nll': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _dp, _vp, _ip]),
@@ -379,6 +380,41 @@ class Handle:
         self.lib.check(self.lib.dll.gpmpc_rollout_multi(self.h, M, codes.ctypes.data_as(ctypes.c_void_p), T, _ptr(z0), _ptr(U),
                                                         _ptr(Sigma0), _ptr(sa), _ptr(sb), _ptr(mean), _ptr(cov)))
         return mean, cov
+
+    def rollout_multi_feedback(self, methods, z0, Sigma0, Kz, k0, Kc, closed=None, U=None, sa=None, sb=None, T=None):
+        """M roll-outs in lock-step, each under its own state feedback or open loop (gpmpc_rollout_multi_feedback): methods[M],
+        z0[M,d], Sigma0[M,d,d], Kz[M,Nu,Ny], k0[M,Nu], Kc[M,Nu,Ny] (one z0 / Sigma0 / gain serves all M), closed[M] (None: all
+        closed), U[M,T,Nu] or [T,Nu]: the controls of the open trajectories.  T comes from U when given, otherwise from T=.
+        Gains may be None when no trajectory is closed.  Returns mean[M,T,Ny], cov[M,T,Ny,Ny], U[M,T,Nu] (controls applied)."""
+        codes = np.array([METHODS[m] if isinstance(m, str) else int(m) for m in methods], dtype=np.int32)
+        M, Nu, Ny, d = len(codes), self.d - self.Ny, self.Ny, self.d
+        nu1 = max(Nu, 1)
+
+        def per_traj(a, *shape):
+            return None if a is None else np.ascontiguousarray(np.broadcast_to(_f64(a).reshape((-1,) + shape), (M,) + shape))
+        z0, Sigma0 = per_traj(z0, d), per_traj(Sigma0, d, d)
+        Kz, k0, Kc = (per_traj(Kz, Nu, Ny), per_traj(k0, Nu), per_traj(Kc, Nu, Ny)) if Nu > 0 else (None, None, None)
+        sa = None if sa is None else _f64(sa).reshape(Ny)
+        sb = None if sb is None else _f64(sb).reshape(Ny)
+        if U is not None and Nu > 0:
+            U = np.asarray(U, dtype=np.float64)
+            if T is not None and int(T) != U.shape[-2]:
+                raise ValueError(f'T = {T} but U holds {U.shape[-2]} steps')
+            T = U.shape[-2]
+            U = per_traj(U, T, Nu)
+        else:
+            U = None
+        if T is None:
+            raise ValueError('rollout_multi_feedback needs U or T=')
+        T = int(T)
+        if closed is not None:
+            closed = np.ascontiguousarray(np.broadcast_to(np.asarray(closed).astype(bool).astype(np.int32).reshape(-1), (M,)))
+        mean, cov, Uo = np.zeros((M, T, Ny)), np.zeros((M, T, Ny, Ny)), np.zeros((M, T, nu1))
+        self.lib.check(self.lib.dll.gpmpc_rollout_multi_feedback(
+            self.h, M, codes.ctypes.data_as(ctypes.c_void_p), T, _ptr(z0), _ptr(Sigma0),
+            _ptr(sa), _ptr(sb), None if closed is None else closed.ctypes.data_as(ctypes.c_void_p), _ptr(Kz), _ptr(k0), _ptr(Kc), _ptr(U),
+            _ptr(mean), _ptr(cov), _ptr(Uo) if Nu > 0 else None))
+        return mean, cov, Uo[:, :, :Nu]
 
     def rollout_feedback(self, method, T, z0, Sigma0, Kz, k0, Kc, sa=None, sb=None):
         """Roll-out with state feedback u_t = Kz mean_{t-1} + k0 (include/gpmpc.h): mean[T,Ny], cov[T,Ny,Ny], U[T,Nu]."""

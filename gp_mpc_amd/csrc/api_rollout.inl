@@ -161,14 +161,28 @@ extern "C" int gpmpc_rollout_feedback(gpmpc_gp* h, int method, int T, const doub
 // a roll-out at C3 size), the trajectories of a moment method one batched launch set.  Trajectories are independent: a
 // trajectory's numbers do not depend on what else is in the call, with one exception spelt out in include/gpmpc.h (a lone
 // 'ME' / 'TA' trajectory takes the one-column variance kernel, two or more the batched one: two summation orders).
-extern "C" int gpmpc_rollout_multi(gpmpc_gp* h, int M, const int* methods, int T, const double* z0, const double* U,
-                                   const double* Sigma0, const double* sa, const double* sb, double* mean, double* cov) {
+//
+// fb (gpmpc_rollout_multi_feedback): trajectory m with closed[m] != 0 (closed == NULL: every one) runs under the reference's
+// state feedback (predict_compare(feedback=True), gp_class.py:787-804) with its own gains Kz[m], k0[m], Kc[m], exactly as
+// gpmpc_rollout_feedback runs one; the others take their controls from U.  The batches and queues are the open-loop call's:
+// only the hand-over between two steps differs (rollout_feed_multi_fb_kernel), and the gains ride in the one upload.
+// Without fb this is gpmpc_rollout_multi as it always was: same staging layout, same launches, same bits.
+static int rollout_multi_impl(gpmpc_gp* h, int M, const int* methods, int T, const double* z0, const double* U,
+                              const double* Sigma0, const double* sa, const double* sb, bool fb, const int* closed,
+                              const double* Kz, const double* k0, const double* Kc, double* mean, double* cov, double* Uout) {
     if (!h) return fail(GPMPC_EINVAL, "NULL handle");
     if (!h->fitted) return fail(GPMPC_ENOTFIT, "model has no factors (call gpmpc_fit or gpmpc_set_factors)");
     const int d = h->d, Ny = h->Ny, Nu = d - Ny;
-    if (M <= 0 || M > 64 || T <= 0 || !methods || !z0 || !Sigma0 || !mean || !cov || (Nu > 0 && !U))
+    if (M <= 0 || M > 64 || T <= 0 || !methods || !z0 || !Sigma0 || !mean || !cov || (!fb && Nu > 0 && !U))
         return fail(GPMPC_EINVAL, "bad M (1..64), T or NULL argument");
     if (Nu < 0) return fail(GPMPC_EINVAL, "roll-out needs d >= Ny (inputs are [state, control])");
+    auto is_closed = [&](int m) { return fb && (!closed || closed[m] != 0); };
+    if (fb) {
+        int nClosed = 0;
+        for (int m = 0; m < M; ++m) nClosed += is_closed(m) ? 1 : 0;
+        if (nClosed && (Nu == 0 || !Kz || !k0 || !Kc)) return fail(GPMPC_EINVAL, "feedback roll-out needs controls and Kz, k0, Kc");
+        if (nClosed < M && Nu > 0 && !U) return fail(GPMPC_EINVAL, "U is NULL with an open-loop trajectory in the call");
+    }
     for (int m = 0; m < M; ++m) {
         if (methods[m] < GPMPC_ME || methods[m] > GPMPC_OLD_TA) return fail(GPMPC_EINVAL, "No GP method with code %d", methods[m]);
         if (methods[m] == GPMPC_OLD_TA && h->mean_kind)
@@ -186,7 +200,9 @@ extern "C" int gpmpc_rollout_multi(gpmpc_gp* h, int M, const int* methods, int T
     const bool moments = nA < M;
     const int nu1 = std::max(Nu, 1);
     const size_t nZ = (size_t)M * d, nS = (size_t)M * d * d, nU = (size_t)T * M * nu1, nM = (size_t)T * M * Ny, nC = (size_t)T * M * Ny * Ny;
-    const size_t nIn = nZ + nS + 2 * Ny + nU;
+    // (fb: per trajectory, in device order, a flag and the gains [closed (M) | Kz | k0 | Kc] between sb and the controls)
+    const size_t nK = (size_t)M * nu1 * Ny, nG = fb ? (size_t)M + 2 * nK + (size_t)M * nu1 : 0;
+    const size_t nIn = nZ + nS + 2 * Ny + nG + nU;
     const size_t total = nIn + nM + nC + (size_t)M * Ny + (size_t)M * Ny * d;
     if (total > h->rollm_cap) {
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -199,7 +215,8 @@ extern "C" int gpmpc_rollout_multi(gpmpc_gp* h, int M, const int* methods, int T
         h->rollm_cap = total;
     }
     double* buf = h->rollm_dev;
-    double *dZ = buf, *dS = dZ + nZ, *dsa = dS + nS, *dsb = dsa + Ny, *dU = dsb + Ny, *dM = dU + nU, *dC = dM + nM, *dV = dC + nC,
+    double *dZ = buf, *dS = dZ + nZ, *dsa = dS + nS, *dsb = dsa + Ny, *dF = dsb + Ny, *dKz = dF + (fb ? M : 0), *dk0 = dKz + (fb ? nK : 0),
+           *dKc = dk0 + (fb ? (size_t)M * nu1 : 0), *dU = dsb + Ny + nG, *dM = dU + nU, *dC = dM + nM, *dV = dC + nC,
            *dJ = dV + (size_t)M * Ny;
     {
         double* pz = h->rollm_pin;
@@ -208,6 +225,14 @@ extern "C" int gpmpc_rollout_multi(gpmpc_gp* h, int M, const int* methods, int T
             const int m = perm[k];
             std::memcpy(pz + (dZ - buf) + (size_t)k * d, z0 + (size_t)m * d, d * sizeof(double));
             std::memcpy(pz + (dS - buf) + (size_t)k * d * d, Sigma0 + (size_t)m * d * d, (size_t)d * d * sizeof(double));
+            if (is_closed(m)) {                       // (Nu > 0, so nu1 == Nu) its first control comes with z0, the rest from the law
+                pz[(dF - buf) + k] = 1.0;
+                std::memcpy(pz + (dKz - buf) + (size_t)k * Nu * Ny, Kz + (size_t)m * Nu * Ny, (size_t)Nu * Ny * sizeof(double));
+                std::memcpy(pz + (dk0 - buf) + (size_t)k * Nu, k0 + (size_t)m * Nu, Nu * sizeof(double));
+                std::memcpy(pz + (dKc - buf) + (size_t)k * Nu * Ny, Kc + (size_t)m * Nu * Ny, (size_t)Nu * Ny * sizeof(double));
+                std::memcpy(pz + (dU - buf) + (size_t)k * nu1, z0 + (size_t)m * d + Ny, Nu * sizeof(double));
+                continue;
+            }
             for (int t = 0; t < T && Nu > 0; ++t)     // time-major on the device: the controls of step t are one block
                 std::memcpy(pz + (dU - buf) + ((size_t)t * M + k) * nu1, U + ((size_t)m * T + t) * Nu, Nu * sizeof(double));
         }
@@ -237,8 +262,14 @@ extern "C" int gpmpc_rollout_multi(gpmpc_gp* h, int M, const int* methods, int T
     auto feed = [&](int t, int off, int cntg) {  // (mean, cov)_{t-1} and u_t of trajectories [off, off + cntg) -> their next inputs
         const double* pM = dM + (size_t)(t - 1) * M * Ny;
         const double* pC = dC + (size_t)(t - 1) * M * Ny * Ny;
-        hipLaunchKernelGGL(rollout_feed_multi_kernel, dim3(cntg), dim3(64), 0, h->stream, pM + (size_t)off * Ny, pC + (size_t)off * Ny * Ny,
-                           dU + ((size_t)t * M + off) * nu1, dsa, dsb, dZ + (size_t)off * d, dS + (size_t)off * d * d, Ny, d, nu1);
+        if (fb)
+            hipLaunchKernelGGL(rollout_feed_multi_fb_kernel, dim3(cntg), dim3(64), 0, h->stream, pM + (size_t)off * Ny,
+                               pC + (size_t)off * Ny * Ny, dU + ((size_t)t * M + off) * nu1, dsa, dsb, dZ + (size_t)off * d,
+                               dS + (size_t)off * d * d, Ny, d, nu1, dF + off, dKz + (size_t)off * nu1 * Ny, dk0 + (size_t)off * nu1,
+                               dKc + (size_t)off * nu1 * Ny);
+        else
+            hipLaunchKernelGGL(rollout_feed_multi_kernel, dim3(cntg), dim3(64), 0, h->stream, pM + (size_t)off * Ny, pC + (size_t)off * Ny * Ny,
+                               dU + ((size_t)t * M + off) * nu1, dsa, dsb, dZ + (size_t)off * d, dS + (size_t)off * d * d, Ny, d, nu1);
     };
     auto step_a = [&](int t) -> int {            // the 'ME' / 'TA' batch of time step t
         double* oM = dM + (size_t)t * M * Ny;
@@ -291,7 +322,10 @@ extern "C" int gpmpc_rollout_multi(gpmpc_gp* h, int M, const int* methods, int T
         }
     }
     if (rc != GPMPC_OK) { hipStreamSynchronize(h->stream); if (h->side_stream) hipStreamSynchronize(h->side_stream); return rc; }
-    hipError_t e = hipMemcpyAsync(h->rollm_pin + (dM - buf), dM, (nM + nC) * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    const bool wantU = fb && Uout && Nu > 0;     // the controls lie in front of the means: still one copy back
+    double* first = wantU ? dU : dM;
+    hipError_t e = hipMemcpyAsync(h->rollm_pin + (first - buf), first, ((wantU ? nU : 0) + nM + nC) * sizeof(double),
+                                  hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return fail(GPMPC_EHIP, "%s", hipGetErrorString(e));
@@ -301,6 +335,22 @@ extern "C" int gpmpc_rollout_multi(gpmpc_gp* h, int M, const int* methods, int T
         for (int t = 0; t < T; ++t) {
             std::memcpy(mean + ((size_t)perm[k] * T + t) * Ny, hM + ((size_t)t * M + k) * Ny, Ny * sizeof(double));
             std::memcpy(cov + ((size_t)perm[k] * T + t) * Ny * Ny, hC + ((size_t)t * M + k) * Ny * Ny, (size_t)Ny * Ny * sizeof(double));
+            if (wantU) std::memcpy(Uout + ((size_t)perm[k] * T + t) * Nu, h->rollm_pin + (dU - buf) + ((size_t)t * M + k) * nu1, Nu * sizeof(double));
         }
     return GPMPC_OK;
+}
+
+extern "C" int gpmpc_rollout_multi(gpmpc_gp* h, int M, const int* methods, int T, const double* z0, const double* U,
+                                   const double* Sigma0, const double* sa, const double* sb, double* mean, double* cov) {
+    return rollout_multi_impl(h, M, methods, T, z0, U, Sigma0, sa, sb, false, nullptr, nullptr, nullptr, nullptr, mean, cov, nullptr);
+}
+
+// Closed-loop roll-outs in lock-step (include/gpmpc.h).  Speed against M consecutive gpmpc_rollout_feedback calls: not measured
+// on the GPU yet (tools/rollout_feedback_ab.py runs the A/B at N = 8192, Ny = 6, d = 8, T = 30); the expectation -- one stream of
+// L^-1 per time step instead of M -- rests on the open-loop record of gpmpc_rollout_multi.
+extern "C" int gpmpc_rollout_multi_feedback(gpmpc_gp* h, int M, const int* methods, int T, const double* z0, const double* Sigma0,
+                                            const double* sa, const double* sb, const int* closed, const double* Kz,
+                                            const double* k0, const double* Kc, const double* U, double* mean, double* cov,
+                                            double* U_out) {
+    return rollout_multi_impl(h, M, methods, T, z0, U, Sigma0, sa, sb, true, closed, Kz, k0, Kc, mean, cov, U_out);
 }

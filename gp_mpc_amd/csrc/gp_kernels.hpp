@@ -802,6 +802,63 @@ __global__ void __launch_bounds__(64) rollout_feed_multi_kernel(const double* __
     for (int e = tid; e < Ny * Ny; e += 64) Sm[(e / Ny) * d + e % Ny] = cp[e];
 }
 
+// The hand-over of M lock-step trajectories of which some run under state feedback (gpmpc_rollout_multi_feedback;
+// predict_compare(feedback=True), gp_class.py:787-804).  Workgroup m serves trajectory m: closed[m] != 0 is
+// rollout_feed_kernel's feedback branch with the gains of that trajectory (u_t = k0[m] + Kz[m] mean_{t-1}, also written to
+// the time-major device copy of the controls; Sigma's control blocks C Kc[m]^T and Kc[m] C Kc[m]^T), closed[m] == 0 is
+// rollout_feed_multi_kernel's copy of the given control.  Every sum is written in rollout_feed_kernel's operation order: a
+// call with one closed trajectory gives the bits of gpmpc_rollout_feedback.  Trajectories do not interact: no fences, no
+// flags.  u_t is read (open) or written (closed), each entry by one thread.  grid (M), 64 threads.
+__global__ void __launch_bounds__(64) rollout_feed_multi_fb_kernel(const double* __restrict__ mean_prev, const double* __restrict__ cov_prev,
+                                                                   double* u_t, const double* __restrict__ sa,
+                                                                   const double* __restrict__ sb, double* __restrict__ z,
+                                                                   double* __restrict__ Sigma, int Ny, int d, int nu1,
+                                                                   const double* __restrict__ closed,
+                                                                   const double* __restrict__ Kz_all,
+                                                                   const double* __restrict__ k0_all,
+                                                                   const double* __restrict__ Kc_all) {
+    const int m = blockIdx.x, tid = threadIdx.x, Nu = d - Ny;
+    const double* mp = mean_prev + (long)m * Ny;
+    const double* cp = cov_prev + (long)m * Ny * Ny;
+    double* up = u_t + (long)m * nu1;
+    double* zm = z + (long)m * d;
+    double* Sm = Sigma + (long)m * d * d;
+    const bool fb = closed[m] != 0.0;
+    const double* Kz = Kz_all + (long)m * nu1 * Ny;
+    const double* k0 = k0_all + (long)m * nu1;
+    const double* Kc = Kc_all + (long)m * nu1 * Ny;
+    for (int e = tid; e < d; e += 64) {
+        double v;
+        if (e < Ny) v = sa[e] * mp[e] + sb[e];
+        else if (fb) {
+            v = k0[e - Ny];
+            for (int c = 0; c < Ny; ++c) v += Kz[(e - Ny) * Ny + c] * mp[c];
+            up[e - Ny] = v;
+        } else v = up[e - Ny];
+        zm[e] = v;
+    }
+    for (int e = tid; e < Ny * Ny; e += 64) Sm[(e / Ny) * d + e % Ny] = cp[e];
+    if (fb) {
+        for (int e = tid; e < Ny * Nu; e += 64) {           // cov_xu = C Kc^T  [Ny x Nu]
+            const int r = e / Nu, q = e % Nu;
+            double v = 0.0;
+            for (int c = 0; c < Ny; ++c) v += cp[r * Ny + c] * Kc[q * Ny + c];
+            Sm[r * d + Ny + q] = v;
+            Sm[(Ny + q) * d + r] = v;
+        }
+        for (int e = tid; e < Nu * Nu; e += 64) {           // covar_u = Kc C Kc^T
+            const int p = e / Nu, q = e % Nu;
+            double v = 0.0;
+            for (int r = 0; r < Ny; ++r) {
+                double t = 0.0;
+                for (int c = 0; c < Ny; ++c) t += cp[r * Ny + c] * Kc[q * Ny + c];
+                v += Kc[p * Ny + r] * t;
+            }
+            Sm[(Ny + p) * d + Ny + q] = v;
+        }
+    }
+}
+
 // Matrix-vector products with the explicit factors (a5: alpha = L^-T (L^-1 y), optimize.py:353-354,494;
 // beta = K^-1 y, gp_functions.py:383).  HBM-read bound: 4 N^2 bytes for a triangular operand.
 // out[i] = sum_{k < (lower ? i+1 : Np)} A[i][k] x[k]: one wave per row, lanes stride the row (512 B

@@ -614,6 +614,88 @@ class GP:
             var = var.clip(min=0)
         return (mean, var, controls) if return_controls else (mean, var)
 
+    ROLLOUT_CLOSED_LOOP_MAX = 64    # trajectories per device call (gpmpc_rollout_multi_feedback's limit)
+
+    def rollout_closed_loop(self, X0, Nt, methods=None, x_ref=None, Q=None, R=None, K=None, u0=None, return_controls=False):
+        """Closed-loop propagation (predict_compare(feedback=True), gp_class.py:772-804) of MANY trajectories in lock-step:
+        for every start state in X0[S, Ny] and every method one trajectory of Nt steps under u_t = K (mean_t - x_ref),
+        all of them advanced together on the device (`gpmpc_rollout_multi_feedback`: one pass over the factors per time
+        step serves every 'ME' / 'TA' trajectory of a call; at most ROLLOUT_CLOSED_LOOP_MAX trajectories per call, more
+        are split over several calls).  The gain is the LQR gain of the model linearised at (start, u0) -- `u0` defaults
+        to zeros -- by `discrete_linearize` + `lqr_gain` under that trajectory's method, unless `K` ([Nu, Ny], or
+        [S, Nu, Ny]: one per start) is given.  Returns mean[S, len(methods), Nt+1, Ny] and var[...] (un-standardised and
+        clipped at 0 like `rollout`), with return_controls=True also the controls applied [S, len(methods), Nt, Nu].
+
+        DIFF: every trajectory starts from the reference's FRESH initial input covariance (eye(Nx) * 1e-6 with the state
+        block diag(sn^2), gp_class.py:764,780).  The reference's loop -- and `rollout(feedback=True)`, which follows it
+        literally -- never resets `covar` between methods: the control blocks method i leaves after its last step are
+        part of method i+1's initial covariance (gp_class.py:777-804), so its methods are not independent trajectories
+        and cannot advance in lock-step.  A single-method `rollout(feedback=True)` is the same trajectory as here."""
+        Nx, Ny, Nu = self.__Nx, self.__Ny, self.__Nu
+        if Nu == 0:
+            raise ValueError('a closed-loop roll-out needs a model with controls')
+        X0 = np.atleast_2d(np.asarray(X0, dtype=np.float64)).reshape(-1, Ny)
+        S, Nt = X0.shape[0], int(Nt)
+        if methods is None:
+            methods = ['EM', 'TA', 'ME']
+        for m in methods:
+            if m not in METHODS:
+                raise NameError('No GP method called: ' + str(m))
+        nm = len(methods)
+        norm = self.__normalize
+        one = np.ones(1)
+        stdX, meanX = (np.atleast_1d(self.__stdX), np.atleast_1d(self.__meanX)) if norm else (one, 0 * one)
+        stdU, meanU = (np.atleast_1d(self.__stdU), np.atleast_1d(self.__meanU)) if norm else (one, 0 * one)
+        stdY, meanY = (np.atleast_1d(self.__stdY), np.atleast_1d(self.__meanY)) if norm else (one, 0 * one)
+        sa = stdY / stdX if norm else None                                        # x_s(next) = sa * mean_s + sb
+        sb = (meanY - meanX) / stdX if norm else None
+        x_ref = np.zeros(Ny) if x_ref is None else np.asarray(x_ref, dtype=np.float64).reshape(Ny)   # gp_class.py:770-771
+        Q = np.eye(Ny) if Q is None else np.asarray(Q, dtype=np.float64)          # :765-768
+        R = np.eye(Nu) if R is None else np.asarray(R, dtype=np.float64)
+        u0 = np.zeros(Nu) if u0 is None else np.asarray(u0, dtype=np.float64).reshape(Nu)
+        if K is not None:
+            K = np.broadcast_to(np.asarray(K, dtype=np.float64).reshape(-1, Nu, Ny), (S, Nu, Ny))
+        covar = np.eye(Nx) * 1e-6                                                 # gp_class.py:764
+        covar[:Ny, :Ny] = np.diag(self.__hyper[:, Nx + 1] ** 2)                   # :780
+        Z0, Kz, k0, Kc = (np.zeros((S, nm, Nx)), np.zeros((S, nm, Nu, Ny)), np.zeros((S, nm, Nu)), np.zeros((S, nm, Nu, Ny)))
+        keep = self.__gp_method
+        for s in range(S):
+            gains = {}
+            for i, m in enumerate(methods):
+                if K is not None:
+                    Km = K[s]
+                else:
+                    kind = 'EM' if m == 'EM' else 'mean'         # (only 'EM' linearises another mean: discrete_linearize)
+                    if kind not in gains:
+                        self.set_method(m)
+                        A, B = self.discrete_linearize(X0[s], u0, covar)          # :785-786
+                        gains[kind] = self.lqr_gain(A, B, Q, R)
+                    Km = gains[kind]
+                u1 = Km @ (X0[s] - x_ref)                                         # :789-790
+                Z0[s, i] = np.concatenate([(X0[s] - meanX) / stdX, (u1 - meanU) / stdU])
+                Kz[s, i] = (Km * stdY[None, :]) / stdU[:, None]
+                k0[s, i] = (Km @ (meanY * np.ones(Ny) - x_ref) - meanU) / stdU
+                Kc[s, i] = Km
+        self.__gp_method = keep
+        flat = lambda a: a.reshape((S * nm,) + a.shape[2:])
+        Z0, Kz, k0, Kc = flat(Z0), flat(Kz), flat(k0), flat(Kc)
+        codes = list(methods) * S
+        mean_s, cov, U_s = np.zeros((S * nm, Nt, Ny)), np.zeros((S * nm, Nt, Ny, Ny)), np.zeros((S * nm, Nt, Nu))
+        for lo in range(0, S * nm, self.ROLLOUT_CLOSED_LOOP_MAX):
+            hi = min(lo + self.ROLLOUT_CLOSED_LOOP_MAX, S * nm)
+            mean_s[lo:hi], cov[lo:hi], U_s[lo:hi] = self._h.rollout_multi_feedback(
+                codes[lo:hi], Z0[lo:hi], covar, Kz[lo:hi], k0[lo:hi], Kc[lo:hi], sa=sa, sb=sb, T=Nt)
+        mean = np.zeros((S, nm, Nt + 1, Ny))
+        var = np.zeros((S, nm, Nt + 1, Ny))
+        mean[:, :, 0, :] = X0[:, None, :]
+        mean[:, :, 1:, :] = (self.inverse_mean(mean_s, self.__meanY, self.__stdY) if norm else mean_s).reshape(S, nm, Nt, Ny)
+        v = np.einsum('ktii->kti', cov)
+        var[:, :, 1:, :] = (self.inverse_variance(v) if norm else v).reshape(S, nm, Nt, Ny)
+        if np.any(var < 0):
+            var = var.clip(min=0)
+        controls = (U_s * stdU + meanU).reshape(S, nm, Nt, Nu)
+        return (mean, var, controls) if return_controls else (mean, var)
+
     def predict_compare(self, x0, u, model=None, num_cols=2, xnames=None, title=None, feedback=False, x_ref=None,
                         Q=None, R=None, methods=None):
         """`predict_compare` (gp_class.py:746-861) without its matplotlib front end: the T-step uncertainty propagation

@@ -217,12 +217,36 @@ int gpmpc_rollout_feedback(gpmpc_gp* h, int method, int T, const double* z0, con
  * as in gpmpc_rollout.  Outputs mean[M x T x Ny], cov[M x T x Ny x Ny].  Per time step ONE pass over the factors serves
  * every trajectory: all 'ME' / 'TA' trajectories form one prediction batch (the lower triangles of L^-1 are streamed once
  * for up to 32 of them -- at N = 8192, Ny = 6 that stream IS the step: 1.6 GB), the trajectories of a moment method
- * one batched launch set.  M <= 64.  Open loop only (gpmpc_rollout_feedback for the reference's feedback law).
+ * one batched launch set.  M <= 64.  Open loop only (gpmpc_rollout_multi_feedback for the reference's feedback law).
  * Parity: trajectories do not influence each other; a trajectory's numbers are bitwise those of gpmpc_rollout when it
  * is the only 'ME' / 'TA' trajectory of the call (or a moment method), and otherwise agree with it to rounding (the
  * batched variance kernel sums the same N terms in another order than the one-column kernel: ~1e-15 sf^2 per step). */
 int gpmpc_rollout_multi(gpmpc_gp* h, int M, const int* methods, int T, const double* z0, const double* U,
                         const double* Sigma0, const double* sa, const double* sb, double* mean, double* cov);
+/* gpmpc_rollout_multi with per-trajectory state feedback: closed-loop roll-outs in lock-step.  Trajectory m with
+ * closed[m] != 0 (closed == NULL: every trajectory) follows the reference's closed-loop propagation
+ * (predict_compare(feedback=True), gp_class.py:787-804: u_t = K (mean_{t-1} - x_ref), input covariance
+ * [[C, C K^T], [K C, K C K^T]]) exactly as gpmpc_rollout_feedback runs it, with its own gains Kz[m] (Kz[M x Nu x Ny]),
+ * k0[m] (k0[M x Nu]) and Kc[m] (Kc[M x Nu x Ny]): Kz / k0 act on the standardised output mean and give u_t in the GP's
+ * input units, Kc acts on the covariance blocks, the state block of Sigma is replaced by cov_{t-1} every step; its first
+ * control comes with z0[m] = [x_0, u_0].  Trajectory m with closed[m] == 0 is an open-loop trajectory of
+ * gpmpc_rollout_multi with the controls U[m] (U[M x T x Nu]); its rows of Kz / k0 / Kc are ignored, as are the rows of U
+ * of a closed trajectory.  U may be NULL when no trajectory is open, the gains when none is closed.  U_out[M x T x Nu]
+ * (may be NULL) returns the controls that were applied (the given ones for an open trajectory).  Host pointers, M <= 64,
+ * all five method codes.  GPMPC_EINVAL: the rules of gpmpc_rollout_multi, and a closed trajectory with Nu = 0 or with a
+ * NULL gain, an open one with U == NULL (Nu > 0).
+ * Per time step the work is gpmpc_rollout_multi's: all 'ME' / 'TA' trajectories, closed and open, form one prediction
+ * batch (ONE stream of L^-1 instead of one per trajectory), the moment-method trajectories one batched launch set; only
+ * the hand-over between two steps differs.  The gains travel in the same upload as z0 / Sigma0 / U.
+ * Parity: a call with one closed trajectory gives the bits of gpmpc_rollout_feedback, a call without a closed one the bits
+ * of gpmpc_rollout_multi; a moment-method trajectory always has the bits of its single call, an 'ME' / 'TA' trajectory next
+ * to another one agrees with its single call to rounding (gpmpc_rollout_multi's note); among calls with 2..32 'ME' / 'TA'
+ * trajectories its bits do not depend on its position or on what else is in the call (a wider batch takes another
+ * variance kernel: rounding again). */
+int gpmpc_rollout_multi_feedback(gpmpc_gp* h, int M, const int* methods, int T, const double* z0, const double* Sigma0,
+                                 const double* sa, const double* sb, const int* closed, const double* Kz,
+                                 const double* k0, const double* Kc, const double* U, double* mean, double* cov,
+                                 double* U_out);
 /* a14 GP.covar gp_class.py:353-381: covar[Ny x n x n] = sf^2 - V^T V for n new inputs. */
 int gpmpc_covar(gpmpc_gp* h, int n, const double* Xnew, double* covar);
 
