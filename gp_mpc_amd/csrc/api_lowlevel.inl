@@ -139,6 +139,16 @@ extern "C" int gpmpc_set_tuning(const char* name, int value) {
         g_em_diag_segs = value;
         return GPMPC_OK;
     }
+    if (std::strcmp(name, "predict_chunk") == 0) {       // predict family: points per scratch chunk at most (0 = the build's own size; tests)
+        if (value != 0 && (value < 64 || value > 32768 || value % 64)) return fail(GPMPC_EINVAL, "predict_chunk must be 0 or a multiple of 64 in [64, 32768]");
+        g_predict_chunk = value;
+        return GPMPC_OK;
+    }
+    if (std::strcmp(name, "em_sens_chunk") == 0) {       // gpmpc_predict_em_sens: inputs per pass at most (0 = by the scratch budget; tests)
+        if (value < 0) return fail(GPMPC_EINVAL, "em_sens_chunk must be >= 0");
+        g_em_sens_chunk = value;
+        return GPMPC_OK;
+    }
     if (std::strcmp(name, "fail_nll_after") == 0) {      // fault injection for the tests of the restart shard's failure paths
         if (value < 0) return fail(GPMPC_EINVAL, "fail_nll_after must be >= 0");
         static const bool testing = getenv("GPMPC_TESTING") && atoi(getenv("GPMPC_TESTING")) != 0;

@@ -3,14 +3,21 @@
 // ------------------------------------------------------------------------------------------------
 // predict
 // ------------------------------------------------------------------------------------------------
+static int g_predict_chunk = 0;     // gpmpc_set_tuning("predict_chunk", n): cap on the points per scratch chunk (0 = none; tests)
+static int g_em_sens_chunk = 0;     // gpmpc_set_tuning("em_sens_chunk", n): cap on the inputs per pass of gpmpc_predict_em_sens (0 = none; tests)
+
 static int chunk_size(const gpmpc_gp* h) {
     const double budget = 2.0e9;  // bytes of KsT scratch
     long c = (long)(budget / (8.0 * h->Np * h->Ny));
     c = c / 64 * 64;
     if (c < 64) c = 64;
     if (c > 32768) c = 32768;
+    if (g_predict_chunk > 0 && c > g_predict_chunk) c = g_predict_chunk;
     return (int)c;
 }
+
+// Points per pass of the chunk loops: the scratch's capacity, or less when "predict_chunk" was lowered on a live handle
+static int chunk_step(const gpmpc_gp* h) { return std::min(h->Bcap, chunk_size(h)); }
 
 // Host-pointer calls with little data (an MPC's shooting nodes at the reference's model sizes): the inputs are staged in
 // a pinned buffer and go up in one copy, every output is a slice of one device block and comes down in one copy.  With a
@@ -269,8 +276,9 @@ static int predict_driver(gpmpc_gp* h, int method, int B, const double* Z, const
         CHK(compute_invK(h->cx(), h->ws));
         h->have_invK = true;
     }
-    for (int b0 = 0; b0 < B; b0 += h->Bcap) {
-        const int nb = (B - b0 < h->Bcap) ? B - b0 : h->Bcap;
+    const int step = chunk_step(h);
+    for (int b0 = 0; b0 < B; b0 += step) {
+        const int nb = (B - b0 < step) ? B - b0 : step;
         const double* dZ = Z + (size_t)b0 * d;
         const double* dS = Sigma ? Sigma + (size_t)b0 * d * d : nullptr;
         const bool up_sigma = dS && cov && need_sigma;
@@ -401,8 +409,9 @@ extern "C" int gpmpc_predict_sens(gpmpc_gp* h, int B, const double* Z, double* m
         HIPCHK(hipMalloc(&h->sensV, (size_t)h->Bcap * Ny * d * sizeof(double)));
     }
     const Ctx cx = h->cx();
-    for (int b0 = 0; b0 < B; b0 += h->Bcap) {
-        const int nb = (B - b0 < h->Bcap) ? B - b0 : h->Bcap;
+    const int step = chunk_step(h);
+    for (int b0 = 0; b0 < B; b0 += step) {
+        const int nb = (B - b0 < step) ? B - b0 : step;
         const double* dZ = Z + (size_t)b0 * d;
         const size_t cZ = (size_t)nb * d, cM = (size_t)nb * Ny, cJ = cM * d, cH = cJ * d;
         IoPack io;
@@ -498,6 +507,7 @@ extern "C" int gpmpc_predict_em_sens(gpmpc_gp* h, int B, const double* Z, const 
     const int P = Ny * (Ny + 1) / 2, PO = Ny * Ny, tiles = Np / 64;
     const size_t per_in = (size_t)PO * ((size_t)EM_OPS_ORD * Np + (size_t)tiles * EM_NSS + EM_NSS) * sizeof(double);
     int Bc = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, ((size_t)512 << 20) / per_in));
+    if (g_em_sens_chunk > 0) Bc = std::min(Bc, g_em_sens_chunk);      // (the scratch sizes below follow the capped Bc)
     // one device block: [Z | Sigma | mean | cov | dm_dz | dm_dS | dc_dz | dc_dS | prep | ops | part | sums]
     const size_t nZ = (size_t)B * d, nS = (size_t)B * d * d, nM = (size_t)B * Ny, nC = (size_t)B * Ny * Ny;
     const size_t n1 = nM * d, n2 = nM * d * d, n3 = nC * d, n4 = nC * d * d;

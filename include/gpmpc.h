@@ -342,6 +342,11 @@ int gpmpc_schedule_stats(int mode, int tilesM, int tilesN, int batch, int K, int
  * "em_diag_segs": the a == b pair sums of the same (the ones that stream K^-1): n > 0 = the lower triangle of tiles in n equal
  * ranges per pair (default: four workgroups per CU shared by the outputs, at most one per partial-sum slot; or
  * GPMPC_EM_DIAG_SEGS), 0 = by strips and chunks like the a != b pairs, -1 back to the default; results agree to rounding.
+ * "predict_chunk": n = a multiple of 64 in [64, 32768] caps the points per pass of every chunk loop of the predict family
+ * (gpmpc_predict_mean_var, gpmpc_mean_jac, gpmpc_predict_jac, gpmpc_predict, gpmpc_predict_sens; the single-chunk limits of
+ * gpmpc_covar and of the routes next to a fit follow it), also on a handle whose scratch is already allocated; 0 back to the
+ * build's own size (2e9 bytes of cross-covariances, at most 32768 points).  For tests: the multi-chunk paths at small sizes.
+ * "em_sens_chunk": n >= 1 caps the inputs per pass of gpmpc_predict_em_sens (default: 512 MB of operands); 0 back to that.
  * Returns GPMPC_EINVAL for an unknown name or value. */
 int gpmpc_set_tuning(const char* name, int value);
 

@@ -553,6 +553,33 @@ def _em_scale(invK, X, Y, H, mu, Sigma):
     return scale
 
 
+def moment_bars(invK, X, Y, H, Z, S, em=None, old_me=None, old_ta=None, tol=1e-10):
+    """The bars of check_moment_methods for (mean, cov) of 'EM' / 'old_ME' / 'old_TA' at the rows of Z, S against the oracle
+    restatement fed the same K^-1; shared with the chunked calls (check_chunked_methods)."""
+    d = X.shape[1]
+    sf2 = H[:, d] ** 2
+    msc = np.array([np.sum(np.abs(invK[a] @ Y[:, a])) * sf2[a] for a in range(len(H))])
+    kscale = np.array([np.sum(np.abs(invK[a])) * sf2[a] ** 2 for a in range(len(H))])
+    for b in range(len(Z)):
+        if em is not None:
+            m, c = em
+            om, oc = go.exact_moment(invK, X, Y, H, Z[b], S[b])
+            sc = _em_scale(invK, X, Y, H, Z[b], S[b])
+            assert np.max(np.abs(m[b] - om) / msc) <= tol
+            assert np.max(np.abs(c[b] - oc) / (sc + sf2.max())) <= 10 * tol, (b, np.abs(c[b] - oc).max(), sc.max())
+            assert np.array_equal(c[b], c[b].T)
+        if old_me is not None:
+            m1, c1 = old_me
+            o1m, o1c = go.old_me(invK, X, Y, H, Z[b])
+            assert np.max(np.abs(m1[b] - o1m) / msc) <= tol
+            assert np.max(np.abs(np.diag(c1[b]) - np.diag(o1c)) / kscale) <= tol
+        if old_ta is not None:
+            m2, c2 = old_ta
+            o2m, o2c = go.old_ta(invK, X, Y, H, Z[b], S[b])
+            assert np.max(np.abs(m2[b] - o2m) / msc) <= tol
+            assert np.max(np.abs(c2[b] - o2c)) <= 1e-6 * max(np.abs(o2c).max(), kscale.max() * 1e-4)
+
+
 def check_moment_methods(lib, g=None):
     """a11 'EM' and a12 'old_ME'/'old_TA' against the oracle restatement (same K^-1 fed to both)."""
     if g is None:
@@ -570,21 +597,7 @@ def check_moment_methods(lib, g=None):
     m, c = h.predict('EM', Z, S)
     m1, c1 = h.predict('old_ME', Z)
     m2, c2 = h.predict('old_TA', Z, S)
-    sf2 = H[:, d] ** 2
-    for b in range(len(Z)):
-        om, oc = go.exact_moment(f['invK'], X, Y, H, Z[b], S[b])
-        sc = _em_scale(f['invK'], X, Y, H, Z[b], S[b])
-        msc = np.array([np.sum(np.abs(f['invK'][a] @ Y[:, a])) * sf2[a] for a in range(len(H))])
-        assert np.max(np.abs(m[b] - om) / msc) <= tol
-        assert np.max(np.abs(c[b] - oc) / (sc + sf2.max())) <= 10 * tol, (b, np.abs(c[b] - oc).max(), sc.max())
-        assert np.array_equal(c[b], c[b].T)
-        o1m, o1c = go.old_me(f['invK'], X, Y, H, Z[b])
-        kscale = np.array([np.sum(np.abs(f['invK'][a])) * sf2[a] ** 2 for a in range(len(H))])
-        assert np.max(np.abs(m1[b] - o1m) / msc) <= tol
-        assert np.max(np.abs(np.diag(c1[b]) - np.diag(o1c)) / kscale) <= tol
-        o2m, o2c = go.old_ta(f['invK'], X, Y, H, Z[b], S[b])
-        assert np.max(np.abs(m2[b] - o2m) / msc) <= tol
-        assert np.max(np.abs(c2[b] - o2c)) <= 1e-6 * max(np.abs(o2c).max(), kscale.max() * 1e-4)
+    moment_bars(f['invK'], X, Y, H, Z, S, em=(m, c), old_me=(m1, c1), old_ta=(m2, c2), tol=tol)
     h.close()
 
 
@@ -905,7 +918,7 @@ def check_sensitivities(lib, g, nprobe=12):
     cond = max(np.linalg.cond(f['chol'][a]) ** 2 for a in range(H.shape[0]))
     tol = max(1e-10, 50 * np.finfo(float).eps * cond)                     # u = K^-1 ks is cond-limited
     assert np.max(np.abs(dvar - odv) / (sf2 / ell_min)[None, :, None]) <= tol
-    # chunked evaluation (more points than fit one scratch chunk is not reachable here; at least B = 1)
+    # another batch size (more points than fit one scratch chunk: check_chunked_sens; here B = 1)
     m1, v1, J1, H1, d1 = h.predict_sens(Z[:1])
     assert np.allclose(H1, Hm[:1], rtol=0, atol=1e-12 * np.abs(Hm).max()) and np.allclose(d1, dvar[:1], rtol=0, atol=1e-12 * np.abs(dvar).max() + 1e-300)
     h.close()
@@ -2701,3 +2714,362 @@ def check_random_shapes(lib, n_cases=10, seed=2024, nmax=220):
         assert abs(v - ovv) <= 1e-10 * (abs(ovv) + N), tag
         assert np.max(np.abs(g - og)) <= 1e-7 * (np.abs(og).max() + 1e-3), tag
         h.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# The multi-chunk paths of the predict family at small sizes (tuning knobs 'predict_chunk' / 'em_sens_chunk')
+# ---------------------------------------------------------------------------------------------
+# Every batched entry point loops `for (b0 = 0; b0 < B; b0 += chunk)` and offsets Z, Sigma and every output by b0; the chunk
+# is a constant of the build (2e9 bytes of cross-covariances, at most 32768 points; 512 MB of operands for the 'EM'
+# derivatives), so without the knobs a second pass needs production-size batches.  Each chunked call is checked twice:
+#   (a) bitwise against the concatenation of separate calls on the slices Z[k c:(k + 1) c] with the same handle (a slice of
+#       nb points takes exactly the launches of a chunk of nb points; the uncapped call takes other routes by batch size);
+#   (b) against the oracle, with the bars the suite already holds that quantity to.
+_CHUNK_MODELS = {}
+
+
+class ChunkModel:
+    """One fitted model with B test points (Sigma differs from point to point: synthetic_problem) and the oracle's values
+    at them, computed once per library and shape and shared by the chunk checks."""
+
+    def __init__(self, lib, N, d, Ny, B, seed):
+        p = go.synthetic_problem(N, d, Ny, B, seed=seed, sn=0.1)
+        self.X, self.Y, self.H, self.Z, self.S = p['X'], p['Y'], p['hyper'], p['Z'], p['Sigma']
+        self.d, self.Ny, self.B = d, Ny, B
+        self.h = Handle(lib, self.X, self.Y)
+        assert np.all(self.h.fit(self.H, want_invK=True) == 0)
+        self.f = self.h.get_factors(invK=True)
+        self.sf2, self.ell_min = self.H[:, d] ** 2, self.H[:, :d].min(axis=1)
+        self.om, self.ov, self.oJ = go.mean_var_jac(self.Z, self.X, self.H, self.f['alpha'], self.f['chol'])
+        self.ms = mean_scale(self.X, self.Z, self.H, self.f['alpha'])
+        self._sens = None
+
+    def sens(self):
+        if self._sens is None:
+            self._sens = go.mean_var_sens(self.Z, self.X, self.H, self.f['alpha'], self.f['chol'])
+        return self._sens
+
+    def mean_var_bars(self, mean=None, var=None, tag=None):
+        n = len(mean if mean is not None else var)
+        if mean is not None:
+            assert np.max(np.abs(mean - self.om[:n]) / self.ms[:n]) <= 1e-10, tag
+        if var is not None:
+            assert np.max(np.abs(var - self.ov[:n]) / self.sf2) <= 1e-10, tag
+
+    def jac_bars(self, J, tag=None):                      # check_sensitivities_batches
+        n = len(J)
+        assert np.max(np.abs(J - self.oJ[:n]) / (self.ms[:n] / self.ell_min)[..., None]) <= 1e-10, tag
+
+    def ta_bars(self, cov, S=None, tag=None):             # check_wide_inputs
+        n = len(cov)
+        oc = go.ta_cov(self.ov[:n], self.oJ[:n], self.S[:n] if S is None else S)
+        assert np.max(np.abs(cov - oc)) <= 1e-10 * max(1.0, self.sf2.max()), tag
+
+
+def chunk_model(lib, N=150, d=3, Ny=2, B=165, seed=88):
+    key = (lib.path, N, d, Ny, B, seed)
+    if key not in _CHUNK_MODELS:
+        _CHUNK_MODELS[key] = ChunkModel(lib, N, d, Ny, B, seed)
+    return _CHUNK_MODELS[key]
+
+
+def chunk_slices(B, c):
+    return [(k, min(k + c, B)) for k in range(0, B, c)]
+
+
+def same_bits_as_slices(call, c, *arrays, tag=None):
+    """call(*arrays) -> tuple of outputs with the batch as their first axis.  Runs it on the whole batch (chunked by the
+    library) and on each slice of c points, asserts the same bits, returns the whole batch's outputs."""
+    whole = call(*arrays)
+    parts = [call(*[a[s:e] for a in arrays]) for s, e in chunk_slices(len(arrays[0]), c)]
+    assert len(parts) > 1, 'one chunk: nothing was tested'
+    for i, w in enumerate(whole):
+        cat = np.concatenate([q[i] for q in parts])
+        assert np.array_equal(w, cat), (tag, i, np.argwhere(w != cat)[:4].tolist())
+    return whole
+
+
+def check_chunk_knobs_validation(lib):
+    """'predict_chunk': 0 or a multiple of 64 in [64, 32768]; 'em_sens_chunk': >= 0.  Anything else is GPMPC_EINVAL and
+    leaves the knob where it was."""
+    from gp_mpc_amd._lib import GpmpcError, EINVAL
+    try:
+        for name, bad in (('predict_chunk', (63, 100, -64, 32832)), ('em_sens_chunk', (-1,))):
+            for v in bad:
+                try:
+                    lib.set_tuning(name, v)
+                    assert False, (name, v)
+                except GpmpcError as e:
+                    assert e.code == EINVAL, (name, v, e.code)
+        for name, good in (('predict_chunk', (64, 32768, 128, 0)), ('em_sens_chunk', (1, 1000, 0))):
+            for v in good:
+                lib.set_tuning(name, v)
+    finally:
+        lib.set_tuning('predict_chunk', 0)
+        lib.set_tuning('em_sens_chunk', 0)
+
+
+def check_chunked_mean_var(lib):
+    """gpmpc_predict_mean_var, host pointers, 64 points per chunk: B = 165 (chunks 64, 64, 37), B = 128 (an exact multiple:
+    no empty last chunk), B = 65 (the last chunk is one point: the one-row-per-wave variance kernel).  The knob is lowered
+    on the live handle (its scratch was allocated by an uncapped call before)."""
+    mdl = chunk_model(lib)
+    h = mdl.h
+    h.predict_mean_var(mdl.Z)                             # scratch for 165 points: the loops must step by the cap, not by it
+    try:
+        lib.set_tuning('predict_chunk', 64)
+        for B in (165, 128, 65):
+            mean, var = same_bits_as_slices(h.predict_mean_var, 64, mdl.Z[:B], tag=B)
+            mdl.mean_var_bars(mean, var, tag=B)
+    finally:
+        lib.set_tuning('predict_chunk', 0)
+
+
+def check_chunked_jac_copy_routes(lib, N=150, d=6, Ny=3, B=1100):
+    """gpmpc_predict_jac('TA') with 512 points per chunk: 72 doubles per point, so a chunk carries more than the pinned
+    block of the packed copies (32768 doubles) and goes up and down array by array, chunks 512, 512, 76; and with 64 points
+    per chunk through the packed block (18 chunks)."""
+    mdl = chunk_model(lib, N, d, Ny, B, seed=89)
+    h = mdl.h
+    try:
+        for cap in (512, 64):
+            lib.set_tuning('predict_chunk', cap)
+            mean, cov, J = same_bits_as_slices(lambda Z, S: h.predict_jac('TA', Z, S), cap, mdl.Z, mdl.S, tag=cap)
+            mdl.mean_var_bars(mean, tag=cap)
+            mdl.jac_bars(J, tag=cap)
+            mdl.ta_bars(cov, tag=cap)
+    finally:
+        lib.set_tuning('predict_chunk', 0)
+
+
+def check_chunked_methods(lib, Bm=70):
+    """64 points per chunk, B = 165: gpmpc_mean_jac, gpmpc_predict with 'ME' and 'TA'; the first Bm points with the three
+    moment methods (operands per input: 'EM' is the expensive one)."""
+    mdl = chunk_model(lib)
+    h, Z, S = mdl.h, mdl.Z, mdl.S
+    Ny = mdl.Ny
+    try:
+        lib.set_tuning('predict_chunk', 64)
+        mean, J = same_bits_as_slices(h.mean_jac, 64, Z, tag='mean_jac')
+        mdl.mean_var_bars(mean, tag='mean_jac')
+        mdl.jac_bars(J, tag='mean_jac')
+        m, c = same_bits_as_slices(lambda z: h.predict('ME', z), 64, Z, tag='ME')
+        mdl.mean_var_bars(m, np.einsum('baa->ba', c), tag='ME')
+        assert np.all(c[:, ~np.eye(Ny, dtype=bool)] == 0.0)
+        m, c = same_bits_as_slices(lambda z, s: h.predict('TA', z, s), 64, Z, S, tag='TA')
+        mdl.mean_var_bars(m, tag='TA')
+        mdl.ta_bars(c, tag='TA')
+        Zm, Sm = Z[:Bm], S[:Bm] * 30                      # (the input covariances of check_moment_methods)
+        em = same_bits_as_slices(lambda z, s: h.predict('EM', z, s), 64, Zm, Sm, tag='EM')
+        ome = same_bits_as_slices(lambda z: h.predict('old_ME', z), 64, Zm, tag='old_ME')
+        ota = same_bits_as_slices(lambda z, s: h.predict('old_TA', z, s), 64, Zm, Sm, tag='old_TA')
+        moment_bars(mdl.f['invK'], mdl.X, mdl.Y, mdl.H, Zm, Sm, em=em, old_me=ome, old_ta=ota)
+    finally:
+        lib.set_tuning('predict_chunk', 0)
+
+
+def check_chunked_sens(lib):
+    """gpmpc_predict_sens, 64 points per chunk, B = 165: the VT / UT passes and the Hessian / variance-gradient staging per
+    chunk; bars of check_sensitivities_batches."""
+    mdl = chunk_model(lib)
+    try:
+        lib.set_tuning('predict_chunk', 64)
+        mean, var, J, Hm, dvar = same_bits_as_slices(mdl.h.predict_sens, 64, mdl.Z, tag='sens')
+        oH, odv = mdl.sens()
+        mdl.mean_var_bars(mean, var)
+        mdl.jac_bars(J)
+        assert np.max(np.abs(Hm - oH) / (mdl.ms / mdl.ell_min ** 2)[..., None, None]) <= 1e-10
+        assert np.max(np.abs(dvar - odv) / (mdl.sf2 / mdl.ell_min)[None, :, None]) <= 1e-10, np.max(np.abs(dvar - odv))
+    finally:
+        lib.set_tuning('predict_chunk', 0)
+
+
+def check_chunked_device_pointers(lib, fill=-7.25):
+    """Device-pointer mode, 64 points per chunk, B = 165: the outputs are offset by b0 inside the caller's arrays.  Every
+    output array is one chunk longer than needed and pre-filled: the tail comes back untouched and the head holds the bits
+    of the host-pointer call."""
+    mdl = chunk_model(lib)
+    h, B, d, Ny = mdl.h, mdl.B, mdl.d, mdl.Ny
+    Sm = mdl.S * 30
+    z, s, sm = DevArray(lib, mdl.Z), DevArray(lib, mdl.S), DevArray(lib, Sm)
+    outs = []
+
+    def out(*shape):
+        outs.append(DevArray(lib, np.full((B + 64,) + shape, fill)))
+        return outs[-1]
+
+    def head_tail(a, host, tag):
+        got = a.numpy()
+        assert np.all(got[B:] == fill), (tag, 'wrote past the end')
+        assert np.array_equal(got[:B], host), (tag, np.argwhere(got[:B] != host)[:4].tolist())
+
+    try:
+        lib.set_tuning('predict_chunk', 64)
+        hm, hv = h.predict_mean_var(mdl.Z)
+        tm, tc = h.predict('TA', mdl.Z, mdl.S)
+        em, ec = h.predict('EM', mdl.Z, Sm)
+        mdl.mean_var_bars(hm, hv)
+        mdl.ta_bars(tc)
+        h.set_pointer_mode(True)
+        m1, v1, m2, c2, m3, c3 = out(Ny), out(Ny), out(Ny), out(Ny, Ny), out(Ny), out(Ny, Ny)
+        h.predict_mean_var_dev(B, z.ptr, m1.ptr, v1.ptr)
+        h.predict_dev('TA', B, z.ptr, s.ptr, m2.ptr, c2.ptr)
+        h.predict_dev('EM', B, z.ptr, sm.ptr, m3.ptr, c3.ptr)
+        h.synchronize()
+        for a, host, tag in ((m1, hm, 'mean'), (v1, hv, 'var'), (m2, tm, 'TA mean'), (c2, tc, 'TA cov'), (m3, em, 'EM mean'),
+                             (c3, ec, 'EM cov')):
+            head_tail(a, host, tag)
+    finally:
+        h.set_pointer_mode(False)
+        lib.set_tuning('predict_chunk', 0)
+        for a in [z, s, sm] + outs:
+            a.free()
+
+
+def check_chunked_mean_function(lib, N=150, d=3, Ny=2, B=130, seed=31):
+    """A linear prior mean added to the prediction (build_gp(meanFunc=...)), 64 points per chunk, B = 130: the kernel that
+    adds m(z) and dm/dz gets the chunk's inputs.  Bars of check_mean_functions."""
+    p = go.synthetic_problem(N, d, Ny, B, seed=seed, sn=0.1)
+    X, Y, Hk, Z, S = p['X'], p['Y'], p['hyper'], p['Z'], p['Sigma']
+    Y = Y + 0.4 + 0.3 * X[:, :1]
+    H = np.hstack([Hk, np.random.default_rng(seed).uniform(-0.3, 0.3, (Ny, go.mean_param_count('linear', d)))])
+    o = go.fit_mean(X, Y, H, 'linear')
+    h = Handle(lib, X, Y)
+    try:
+        h.set_mean_func('linear', True)
+        assert np.all(h.fit(H) == 0)
+        lib.set_tuning('predict_chunk', 64)
+        mean, cov, J = same_bits_as_slices(lambda z, s: h.predict_jac('TA', z, s), 64, Z, S)
+        m2, var = same_bits_as_slices(h.predict_mean_var, 64, Z)
+        ms = mean_scale(X, Z, Hk, o['alpha'])
+        om, ov, oJ = go.mean_var_jac(Z, X, H, o['alpha'], o['chol'], mean_func='linear')
+        assert np.max(np.abs(mean - om) / (ms + 1.0)) <= 1e-10
+        assert np.max(np.abs(J - oJ)) <= 1e-10 * max(1.0, np.abs(oJ).max())
+        assert np.max(np.abs(cov - go.ta_cov(ov, oJ, S))) <= 1e-10
+        assert np.array_equal(m2, mean) and np.max(np.abs(var - ov)) <= 1e-10
+    finally:
+        lib.set_tuning('predict_chunk', 0)
+        h.close()
+
+
+def check_em_sens_chunks(lib, N=100, shapes=((4, 3, 13), (9, 2, 9)), B=5):
+    """gpmpc_predict_em_sens with two inputs per pass, B = 5 (passes of 2, 2, 1): its kernels index partly with the global
+    input b0 + bl (prepared matrices, Z, Sigma, mean) and partly with the local one (operands, partial sums, the already
+    offset outputs).  All six outputs carry the bits of the one-pass call -- the arithmetic per input does not depend on
+    the split -- with and without the covariance value; and check_em_sens's oracle comparison runs under the cap.  d = 4
+    (8-deep cross term) and d = 9 (the 16-deep instantiation)."""
+    try:
+        for d, Ny, seed in shapes:
+            p = go.synthetic_problem(N, d, Ny, B, seed=seed, sn=0.1)
+            X, Y, H, Z, S = p['X'], p['Y'], p['hyper'], p['Z'] * 0.5, p['Sigma'] * 40
+            h = Handle(lib, X, Y)
+            h.fit(H, want_invK=True)
+            for want_cov in (True, False):
+                lib.set_tuning('em_sens_chunk', 0)
+                one = h.predict_em_sens(Z, S, want_cov=want_cov)
+                lib.set_tuning('em_sens_chunk', 2)
+                split = h.predict_em_sens(Z, S, want_cov=want_cov)
+                for i, (a, b) in enumerate(zip(one, split)):
+                    if i == 1 and not want_cov:
+                        assert a is None and b is None
+                    else:
+                        assert np.array_equal(a, b), (d, Ny, want_cov, i, np.argwhere(a != b)[:4].tolist())
+            h.close()
+            check_em_sens(lib, N=N, d=d, Ny=Ny, B=B, seed=seed)          # (the cap is still 2)
+    finally:
+        lib.set_tuning('em_sens_chunk', 0)
+
+
+def check_covar_chunks(lib):
+    """gpmpc_covar beyond one 64-column block (n = 70, 130: Bp = 128, 192, ragged) against sf^2 - V^T V, V = L^-1 ks
+    (gp_class.py:353-381) from the oracle's triangular solve with the same factor, at 1e-10 sf^2; symmetric to the rounding
+    of the two sums; and its single-chunk limit under 'predict_chunk' = 64: n = 64 is served, n = 65 is GPMPC_EINVAL."""
+    from scipy.linalg import solve_triangular
+    from gp_mpc_amd._lib import GpmpcError, EINVAL
+    mdl = chunk_model(lib)
+    h, X, H, d = mdl.h, mdl.X, mdl.H, mdl.d
+    Np = -(-len(X) // 64) * 64
+
+    def ref(Zn):
+        out = np.zeros((mdl.Ny, len(Zn), len(Zn)))
+        for a in range(mdl.Ny):
+            V = solve_triangular(mdl.f['chol'][a], go.cov_se_ard_direct(X, Zn, H[a, :d], mdl.sf2[a]), lower=True)
+            out[a] = mdl.sf2[a] - V.T @ V
+        return out
+
+    def bars(cv, Zn):
+        assert np.max(np.abs(cv - ref(Zn)) / mdl.sf2[:, None, None]) <= 1e-10, len(Zn)
+        # entries (i, j) and (j, i) are two fp64 sums of the same Np products v_ki v_kj, sum_k |v_ki v_kj| <= sf^2
+        # (Cauchy-Schwarz, v^T v <= sf^2): each is within Np eps sf^2 of the exact sum in whatever order it is added up
+        asym = np.abs(cv - cv.transpose(0, 2, 1)) / mdl.sf2[:, None, None]
+        assert asym.max() <= 2 * Np * np.finfo(float).eps, (len(Zn), asym.max())
+
+    try:
+        for n in (70, 130):
+            bars(h.covar(mdl.Z[:n]), mdl.Z[:n])
+        lib.set_tuning('predict_chunk', 64)
+        bars(h.covar(mdl.Z[:64]), mdl.Z[:64])
+        try:
+            h.covar(mdl.Z[:65])
+            assert False, 'n = 65 beyond a chunk of 64 was served'
+        except GpmpcError as e:
+            assert e.code == EINVAL, e.code
+    finally:
+        lib.set_tuning('predict_chunk', 0)
+
+
+def check_chunk_routing(lib, N=700, d=3, B=200, seed=91):
+    """More points than one scratch chunk ('predict_chunk' = 64, B = 200, device pointers): gpmpc_fit_predict_mean_var is
+    the two calls and the first prediction behind a fit takes the plain route -- their fast paths are single-chunk -- with
+    the two calls' bits; the counters of both fast routes stay 0.  Oracle bars on the result."""
+    p = go.synthetic_problem(N, d, 1, B, seed=seed, sn=0.1)
+    X, Y, H, Z = p['X'], p['Y'], p['hyper'], p['Z']
+    h = Handle(lib, X, Y)
+    z = DevArray(lib, Z)
+    outs = [DevArray(lib, np.full((B + 64, 1), -7.25)) for _ in range(6)]
+    m0, v0, m1, v1, m2, v2 = outs
+    try:
+        lib.set_tuning('predict_chunk', 64)
+        h.set_pointer_mode(True)
+        i0 = h.fit(H)
+        h.predict_mean_var_dev(B, z.ptr, m0.ptr, v0.ptr)          # the first prediction behind a fit
+        h.predict_mean_var_dev(B, z.ptr, m1.ptr, v1.ptr)          # any later one
+        h.synchronize()
+        i2 = h.fit_predict_mean_var_dev(H, B, z.ptr, m2.ptr, v2.ptr)
+        h.synchronize()
+        assert np.all(i0 == 0) and np.array_equal(i0, i2)
+        assert h.counter('fused_fit_predicts') == 0 and h.counter('predictions_behind_tail') == 0
+        mean, var = m1.numpy(), v1.numpy()
+        for a in outs:
+            assert np.all(a.numpy()[B:] == -7.25)
+        for m, v in ((m0, v0), (m2, v2)):
+            assert np.array_equal(m.numpy(), mean) and np.array_equal(v.numpy(), var)
+        o = go.fit(X, Y, H, want_invK=False)
+        om, ov, _ = go.mean_var_jac(Z, X, H, o['alpha'], o['chol'], False)
+        assert np.max(np.abs(mean[:B] - om) / mean_scale(X, Z, H, o['alpha'])) <= 1e-10
+        assert np.max(np.abs(var[:B] - ov) / H[:, d] ** 2) <= 1e-10
+    finally:
+        lib.set_tuning('predict_chunk', 0)
+        for a in [z] + outs:
+            a.free()
+        h.close()
+
+
+def check_shipped_chunk_boundary(lib, N=100, d=2, Ny=2, extra=100, seed=97):
+    """No knob: the build's own largest chunk.  At Np = 128, Ny = 2 a chunk is 32768 points; B = 32768 + 100 with host
+    pointers runs a full chunk and a second pass of 100.  gpmpc_predict_mean_var and gpmpc_predict_jac('TA') against the
+    oracle."""
+    B = 32768 + extra
+    mdl = ChunkModel(lib, N, d, Ny, B, seed)
+    try:
+        mean, var = mdl.h.predict_mean_var(mdl.Z)
+        mdl.mean_var_bars(mean, var)
+        m2, cov, J = mdl.h.predict_jac('TA', mdl.Z, mdl.S)
+        mdl.mean_var_bars(m2)
+        mdl.jac_bars(J)
+        mdl.ta_bars(cov)
+        # the second pass against a call of its own (a batch of 100 takes the launches of a chunk of 100)
+        mt, vt = mdl.h.predict_mean_var(mdl.Z[32768:])
+        assert np.array_equal(mt, mean[32768:]) and np.array_equal(vt, var[32768:])
+    finally:
+        mdl.h.close()

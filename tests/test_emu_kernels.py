@@ -367,3 +367,44 @@ def test_emu_em_fixed_input_schedules(emu):
 
 def test_emu_em_fixed_input_clamp_routing(emu):
     pc.check_em_fixed_input_clamp_routing(emu)
+
+
+# ---- the multi-chunk paths of the predict family ('predict_chunk' / 'em_sens_chunk': pc.same_bits_as_slices + oracle bars) ----
+def test_emu_chunk_knobs_validation(emu):
+    pc.check_chunk_knobs_validation(emu)
+
+
+def test_emu_chunked_mean_var(emu):
+    pc.check_chunked_mean_var(emu)
+
+
+def test_emu_chunked_jac_copy_routes(emu):
+    pc.check_chunked_jac_copy_routes(emu)
+
+
+def test_emu_chunked_methods(emu):
+    pc.check_chunked_methods(emu)
+
+
+def test_emu_chunked_sens(emu):
+    pc.check_chunked_sens(emu)
+
+
+def test_emu_chunked_device_pointers(emu):
+    pc.check_chunked_device_pointers(emu)
+
+
+def test_emu_chunked_mean_function(emu):
+    pc.check_chunked_mean_function(emu)
+
+
+def test_emu_em_sens_chunks(emu):
+    pc.check_em_sens_chunks(emu)
+
+
+def test_emu_covar_chunks(emu):
+    pc.check_covar_chunks(emu)
+
+
+def test_emu_chunk_routing(emu):
+    pc.check_chunk_routing(emu, N=700, d=3, B=200)       # the first shape of test_emu_fused_fit_predict

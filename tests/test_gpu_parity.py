@@ -440,3 +440,49 @@ def test_em_fixed_input_schedules_where_every_tile_matters(lib):
 
 def test_em_fixed_input_clamp_routing(lib):
     pc.check_em_fixed_input_clamp_routing(lib)
+
+
+# ---- the multi-chunk paths of the predict family ('predict_chunk' / 'em_sens_chunk': pc.same_bits_as_slices + oracle bars) ----
+def test_chunk_knobs_validation(lib):
+    pc.check_chunk_knobs_validation(lib)
+
+
+def test_chunked_mean_var(lib):
+    pc.check_chunked_mean_var(lib)
+
+
+def test_chunked_jac_copy_routes(lib):
+    pc.check_chunked_jac_copy_routes(lib)
+
+
+def test_chunked_methods(lib):
+    pc.check_chunked_methods(lib)
+
+
+def test_chunked_sens(lib):
+    pc.check_chunked_sens(lib)
+
+
+def test_chunked_device_pointers(lib):
+    pc.check_chunked_device_pointers(lib)
+
+
+def test_chunked_mean_function(lib):
+    pc.check_chunked_mean_function(lib)
+
+
+def test_em_sens_chunks(lib):
+    pc.check_em_sens_chunks(lib)
+
+
+def test_covar_chunks(lib):
+    pc.check_covar_chunks(lib)
+
+
+def test_chunk_routing(lib):
+    pc.check_chunk_routing(lib, N=700, d=3, B=200)
+
+
+def test_shipped_chunk_boundary_32768(lib):
+    """The one multi-chunk case without the knob: B = 32768 + 100 at N = 100, Ny = 2 (about 70 MB of scratch)."""
+    pc.check_shipped_chunk_boundary(lib)
