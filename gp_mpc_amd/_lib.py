@@ -56,6 +56,7 @@ SIGNATURES = {
     'gpmpc_get_factors': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     'gpmpc_set_factors': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     'gpmpc_append': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
+    'gpmpc_append_select': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp]),
     'gpmpc_predict_mean_var': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
     'gpmpc_mean_jac': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
     'gpmpc_predict_sens': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -337,6 +338,29 @@ class Handle:
         self.info = info
         self.lib.check(rc)
         return info
+
+    def append_select(self, Xcand, Ycand=None, k=None, min_gain=0.0):
+        """Greedy max-variance choice of at most k of the candidate rows (gpmpc_append_select; k None: up to all of them),
+        appended in pick order unless Ycand is None (selection only).  Returns (selected[k_out], gain[k_out])."""
+        Xcand = _f64(Xcand).reshape(-1, self.d)
+        n = Xcand.shape[0]
+        if Ycand is not None:
+            Ycand = _f64(Ycand).reshape(n, self.Ny)
+        k = n if k is None else int(k)
+        sel = np.zeros(max(k, 1), dtype=np.int32)
+        gain = np.zeros(max(k, 1))
+        kout = ctypes.c_int(0)
+        info = np.zeros(self.Ny, dtype=np.int32)
+        rc = self.lib.dll.gpmpc_append_select(self.h, n, _ptr(Xcand), _ptr(Ycand), k, float(min_gain),
+                                              sel.ctypes.data_as(ctypes.c_void_p), _ptr(gain), ctypes.byref(kout),
+                                              info.ctypes.data_as(ctypes.c_void_p))
+        size = ctypes.c_int(0)              # the library is the authority on the size, whether the call succeeded or not
+        self.lib.dll.gpmpc_get_size(self.h, ctypes.byref(size), None, None)
+        self.N = size.value
+        self.info = info
+        self.selected, self.gain = sel[:kout.value].copy(), gain[:kout.value].copy()
+        self.lib.check(rc)
+        return self.selected, self.gain
 
     def predict_jac(self, method, Z, Sigma=None):
         """mean[B,Ny], cov[B,Ny,Ny] ('ME'/'TA') and J[B,Ny,d] = d mean / d z from one pass."""

@@ -27,6 +27,7 @@
 #include "gemm_f64_dma.hpp"
 #include "gp_kernels.hpp"
 #include "leaf64.hpp"
+#include "select_kernels.hpp"
 #include "train_native.hpp"
 #include "vargemm_persist.hpp"
 
@@ -38,6 +39,7 @@ using namespace gpmpc;
 #include "api_handle.inl"
 #include "api_fit.inl"
 #include "api_predict.inl"
+#include "api_select.inl"
 #include "api_rollout.inl"
 #include "api_train.inl"
 #include "api_lowlevel.inl"

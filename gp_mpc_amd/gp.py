@@ -371,9 +371,38 @@ class GP:
     # ------------------------------------------------------------------ data updates
     def update_data(self, X_new, Y_new, N_new=None):
         """The reference documents its incremental update as not working (gp_class.py:384-471:
-        argmin for 'max variance' :421, norm instead of norm^2 :443); use `update_data_all`."""
+        argmin for 'max variance' :421, norm instead of norm^2 :443); `update_data_select` does what it set out to
+        do, `update_data_all` appends everything."""
         raise NotImplementedError('update_data is broken in the reference (gp_class.py:384-471); '
-                                  'use update_data_all / replace_data_all')
+                                  'use update_data_select (the N_new most informative points), '
+                                  'update_data_all / replace_data_all')
+
+    def update_data_select(self, X_new, Y_new=None, N_new=None, min_gain=0.0):
+        """From the new observations take only the `N_new` most informative ones (default: up to all) -- what the
+        reference's `update_data` intended (gp_class.py:384-471): repeatedly the point whose predictive variance, summed
+        over the outputs, is largest given the model AND the points taken so far (`gpmpc_append_select`).  Differences to
+        the reference's text: arg-max instead of its argmin (:421), the squared norm instead of the norm (:443), and the
+        noise enters only where a taken point joins K (:440) -- the scores are the noise-free variances of `covar`.
+        Selection stops early when the best score (standardised units) falls below `min_gain` (> 0).  The taken rows are
+        appended like `update_data_all` does; `Y_new=None` only selects (experiment design) and changes nothing.
+        Returns (indices into X_new in pick order, their scores when picked)."""
+        X_new = np.array(X_new, dtype=np.float64).copy().reshape(-1, self.__Nx)
+        if Y_new is not None:
+            Y_new = np.array(Y_new, dtype=np.float64).copy().reshape(-1, self.__Ny)
+        if self.__normalize:
+            X_new = self.standardize(X_new, self.__meanZ, self.__stdZ)
+            if Y_new is not None:
+                Y_new = self.standardize(Y_new, self.__meanY, self.__stdY)
+        try:
+            sel, gain = self._h.append_select(X_new, Y_new, N_new, min_gain)
+        finally:
+            grown = self._h.N - self.__N                  # (0 for selection only and when the append was refused)
+            if grown > 0:
+                taken = self._h.selected[:grown]
+                self.__X = np.vstack([self.__X, X_new[taken]])
+                self.__Y = np.vstack([self.__Y, Y_new[taken]])
+                self.__N = self.__X.shape[0]
+        return sel, gain
 
     def _set_data_and_refit(self, X, Y):
         self.__X, self.__Y = X, Y

@@ -153,6 +153,25 @@ int gpmpc_get_factors(gpmpc_gp* h, double* hyper, double* chol, double* alpha, d
  * the factors, O(N^2 n) instead of O(N^3).  info[Ny]: 0 ok, <0 = -(first non-positive pivot); on
  * GPMPC_ENOTPD the model is left unchanged.  Large n (more than a quarter of the new size) refits instead. */
 int gpmpc_append(gpmpc_gp* h, int n, const double* Xnew, const double* Ynew, int* info);
+/* Greedy max-variance selection among n candidates, then gpmpc_append of the chosen rows: what GP.update_data
+ * (gp_class.py:384-471) set out to do -- from n fresh observations keep the N_new most informative ones -- with an arg-MAX
+ * (the reference takes argmin, :421) and the squared norm (it takes the norm, :443).  Xcand[n x d], Ycand[n x Ny]: HOST
+ * pointers in standardised units, whatever the pointer mode.  1 <= k <= n <= the single-chunk limit of gpmpc_covar.
+ * Step t = 0, 1, ...: score_j = sum_a var_a(x_j | training data + the t points picked so far) for every candidate not yet
+ * picked, var_a = the noise-free predictive variance sf_a^2 - |L^-1 ks|^2 (the diagonal of gpmpc_covar) with the stored
+ * hyper-parameters; the pick is the candidate with the largest score, the lowest index among equal scores.  A picked point
+ * enters the model with its noise (k(x, x) + sn^2 [+ the stored jitter], gp_class.py:440); the scores stay noise-free.  If the
+ * best score is < min_gain the selection stops before that pick (min_gain <= 0: never; NaN: GPMPC_EINVAL).
+ * selected[k], gain[k] (the pick's score when it was picked; may be NULL) and *k_out (may be NULL) describe the first k_out
+ * picks.  Unless Ycand == NULL those rows are then appended in pick order: the model is bit for bit the one
+ * gpmpc_append(h, k_out, Xcand[selected], Ycand[selected], info) gives, GPMPC_ENOTPD included (model unchanged; selected / gain /
+ * k_out stay valid).  k_out == 0 leaves the model untouched and returns GPMPC_OK.  Ycand == NULL: selection only (experiment
+ * design: where to measure before any y exists) -- data, factors and N are unchanged.
+ * Work: the candidates' posterior covariance once (O(n^2 N), the GEMMs of gpmpc_covar), then k steps of a jointly pivoted
+ * partial Cholesky of it (O(Ny n t) each, select_kernels.hpp) that never touch the N x N factors, then one append.
+ * GPMPC_ENOTFIT without factors; GPMPC_EINVAL for bad sizes or NULLs (the handle stays usable). */
+int gpmpc_append_select(gpmpc_gp* h, int n, const double* Xcand, const double* Ycand, int k, double min_gain,
+                        int* selected, double* gain, int* k_out, int* info);
 
 /* Import a saved model (GP.load_model -> ctor branch gp_class.py:58-66): chol and hyper are
  * required; alpha == NULL recomputes it from Y; invK == NULL computes it lazily when a method
