@@ -620,7 +620,7 @@ extern "C" int gpmpc_covar(gpmpc_gp* h, int n, const double* Xnew, double* covar
         dZ = h->Z;
     }
     launch_crosscov(cx.stream, d, h->XT, h->ws.hyper, h->ws.alpha, dZ, h->KsT, h->meanT, nullptr, h->N, Np, n, Bp, Ny);
-    double *VT = nullptr, *C = nullptr;
+    double *VT = nullptr, *C = nullptr, *R = nullptr;
     HIPCHK(hipMalloc(&VT, (size_t)Ny * Bp * Np * sizeof(double)));
     HIPCHK(hipMalloc(&C, (size_t)Ny * Bp * Bp * sizeof(double)));
     GemmP p = gemm_base(cx);  // VT[j][i] = sum_k KsT[j][k] invL[i][k]
@@ -629,6 +629,26 @@ extern "C" int gpmpc_covar(gpmpc_gp* h, int n, const double* Xnew, double* covar
     p.C = VT; p.ldc = Np; p.sC = (long)Bp * Np;
     p.M = Bp; p.N = Np; p.K = Np;
     launch_gemm(p, Ny, cx.stream);
+    {
+        // One step of refinement with L itself: V += L^-1 (ks - L V).  A product with the explicitly inverted factor is
+        // 2.5 ... 4 x (rms; single entries up to 50 x) further from the exact sf^2 - ks_i^T K^-1 ks_j than a triangular solve
+        // with L when cond(K) ~ 1e6 (sn = 1e-2; numpy shows the same with an explicit inverse, profiles/var_error_scale.txt);
+        // the residual against L brings the off-diagonal entries back to the solve's error.  Two more products, off the hot path.
+        HIPCHK(hipMalloc(&R, (size_t)Ny * Bp * Np * sizeof(double)));
+        HIPCHK(hipMemcpyAsync(R, h->KsT, (size_t)Ny * Bp * Np * sizeof(double), hipMemcpyDeviceToDevice, cx.stream));
+        GemmP r = gemm_base(cx);  // R[j][i] = KsT[j][i] - sum_k VT[j][k] L[i][k]
+        r.A = VT; r.lda = Np; r.sA = (long)Bp * Np; r.a_mc = 0;
+        r.B = h->ws.L; r.ldb = Np; r.sB = (long)Np * Np; r.b_nc = 0; r.kflags = KB_LE_N;
+        r.C = R; r.ldc = Np; r.sC = (long)Bp * Np;
+        r.M = Bp; r.N = Np; r.K = Np; r.alpha = -1.0; r.beta = 1.0;
+        launch_gemm(r, Ny, cx.stream);
+        GemmP u = gemm_base(cx);  // VT[j][i] += sum_k R[j][k] invL[i][k]
+        u.A = R; u.lda = Np; u.sA = (long)Bp * Np; u.a_mc = 0;
+        u.B = h->ws.Inv; u.ldb = Np; u.sB = (long)Np * Np; u.b_nc = 0; u.kflags = KB_LE_N;
+        u.C = VT; u.ldc = Np; u.sC = (long)Bp * Np;
+        u.M = Bp; u.N = Np; u.K = Np; u.beta = 1.0;
+        launch_gemm(u, Ny, cx.stream);
+    }
     GemmP q = gemm_base(cx);  // C = -VT VT^T
     q.A = VT; q.lda = Np; q.sA = (long)Bp * Np; q.a_mc = 0;
     q.B = VT; q.ldb = Np; q.sB = (long)Bp * Np; q.b_nc = 0;
@@ -640,6 +660,7 @@ extern "C" int gpmpc_covar(gpmpc_gp* h, int n, const double* Xnew, double* covar
     HIPCHK(hipStreamSynchronize(h->stream));
     hipFree(VT);
     hipFree(C);
+    hipFree(R);
     std::vector<double> out((size_t)Ny * n * n);
     for (int a = 0; a < Ny; ++a) {
         const double sf = h->hyper[(size_t)a * h->nh() + d];

@@ -168,22 +168,36 @@ def mean_bars(mean, om, floor=1e-2):
             'mean_pointwise_raw': float((dm / np.maximum(np.abs(om), 1e-300)).max())}
 
 
+def longdouble_kernel(X, Z, hyper_row):
+    """The SE-ARD kernel sf^2 exp(-1/2 sum_k (x_k - z_k)^2 / ell_k^2) of the rows of X against the rows of Z in longdouble,
+    by direct differences: [len(X), len(Z)]."""
+    ld = np.longdouble
+    d = X.shape[1]
+    Xl, Zl = X.astype(ld) / hyper_row[:d].astype(ld), Z.astype(ld) / hyper_row[:d].astype(ld)
+    D = np.zeros((len(X), len(Z)), dtype=ld)
+    for k in range(d):
+        diff = Xl[:, k:k + 1] - Zl[:, k][None, :]
+        D += diff * diff
+    return ld(hyper_row[d]) ** 2 * np.exp(ld(-0.5) * D)
+
+
+def longdouble_gram(X, hyper_row):
+    """K = k(X, X) + sn^2 I in longdouble and the fp64 Cholesky factor (scipy cho_factor, lower) of its rounding, the
+    preconditioner of the refinements below."""
+    from scipy.linalg import cho_factor
+    K = longdouble_kernel(X, X, hyper_row)
+    K[np.diag_indices_from(K)] += np.longdouble(hyper_row[X.shape[1] + 1]) ** 2
+    return K, cho_factor(K.astype(np.float64), lower=True)
+
+
 def longdouble_alpha(X, y, hyper_row, iters=4):
     """alpha = K^-1 y to extended precision (x87 80-bit, eps 1.1e-19; TEST ONLY): the exact SE-ARD kernel in longdouble
     (direct differences), the fp64 Cholesky of its rounding as the preconditioner, `iters` steps of iterative refinement
     with the residual y - K alpha formed in longdouble -- every step gains ~ -log10(cond(K) eps64) digits (cond <= 1e8
     here: >= 8).  Returns (alpha, K) as longdouble arrays."""
-    from scipy.linalg import cho_factor, cho_solve
+    from scipy.linalg import cho_solve
     ld = np.longdouble
-    d = X.shape[1]
-    Xl = X.astype(ld) / hyper_row[:d].astype(ld)
-    D = np.zeros((len(X), len(X)), dtype=ld)
-    for k in range(d):
-        diff = Xl[:, k:k + 1] - Xl[:, k][None, :]
-        D += diff * diff
-    K = ld(hyper_row[d]) ** 2 * np.exp(ld(-0.5) * D)
-    K[np.diag_indices_from(K)] += ld(hyper_row[d + 1]) ** 2
-    cf = cho_factor(K.astype(np.float64), lower=True)
+    K, cf = longdouble_gram(X, hyper_row)
     yl = y.astype(ld)
     alpha = cho_solve(cf, y).astype(ld)
     for _ in range(iters):
@@ -206,6 +220,43 @@ def longdouble_mean(X, hyper_row, alpha_ld, Z):
             D += diff * diff
         out[b0:b0 + 256] = (ld(hyper_row[d]) ** 2 * np.exp(ld(-0.5) * D)).T @ alpha_ld
     return out
+
+
+def longdouble_variance(X, hyper_row, Zs, iters=4):
+    """The noise-free predictive variance sf^2 - ks^T K^-1 ks at the rows of Zs to extended precision (TEST ONLY), with the
+    parts of longdouble_alpha: K and ks in longdouble by direct differences, v = K^-1 ks for all probes at once from the fp64
+    Cholesky of the rounded K, `iters` steps of refinement with the residual ks - K v formed in longdouble (cond(K) <= 1e8).
+    From the same v: the quadratic form Q = ks^T K^-1 ks' of every pair of probes, the posterior covariance k(z, z') - Q,
+    and dvar/dz = -2 (d ks/dz)^T K^-1 ks with d ks_i/dz_p = ks_i (X_ip - z_p) / ell_p^2.  Returns a dict of longdouble
+    arrays: var[B], quad[B, B], cov[B, B], dvar[B, d], dvar_abs[B, d] (the sum of the absolute values of dvar's terms).
+    iters may be a tuple of increasing step counts: one dict per count, from one run of the refinement (the yardstick
+    certifies itself by the difference of two of them)."""
+    from scipy.linalg import cho_solve
+    ld = np.longdouble
+    d = X.shape[1]
+    counts = (iters,) if np.isscalar(iters) else tuple(iters)
+    K, cf = longdouble_gram(X, hyper_row)
+    ks = longdouble_kernel(X, Zs, hyper_row)                          # [N, B]
+    kzz = longdouble_kernel(Zs, Zs, hyper_row)
+    ell2 = hyper_row[:d].astype(ld) ** 2
+    R = [(X[:, p:p + 1].astype(ld) - Zs[:, p].astype(ld)[None, :]) / ell2[p] for p in range(d)]
+
+    def result(v):
+        quad = ks.T @ v
+        quad = (quad + quad.T) / ld(2)
+        w = ks * v
+        dvar = np.stack([ld(-2) * np.sum(w * R[p], axis=0) for p in range(d)], axis=1)
+        dvar_abs = np.stack([ld(2) * np.sum(np.abs(w * R[p]), axis=0) for p in range(d)], axis=1)
+        return dict(var=ld(hyper_row[d]) ** 2 - np.diag(quad), quad=quad, cov=kzz - quad, dvar=dvar, dvar_abs=dvar_abs)
+
+    out = []
+    v = cho_solve(cf, ks.astype(np.float64)).astype(ld)
+    for step in range(1, counts[-1] + 1):
+        r = ks - K @ v
+        v = v + cho_solve(cf, r.astype(np.float64)).astype(ld)
+        if step in counts:
+            out.append(result(v))
+    return out[0] if np.isscalar(iters) else out
 
 
 def check_mean_against_extended_precision(lib, N, d, B, sn, nprobe=1000, seed=1234):
