@@ -57,6 +57,7 @@ SIGNATURES = {
     'gpmpc_set_factors': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     'gpmpc_append': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
     'gpmpc_append_select': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    'gpmpc_remove': (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
     'gpmpc_predict_mean_var': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
     'gpmpc_mean_jac': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
     'gpmpc_predict_sens': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -265,7 +266,7 @@ class Handle:
     def counter(self, name):
         """'handoff_timeouts' | 'chained_factorisations' | 'single_queue_factorisations' | 'workspace_blocks_fresh' |
         'workspace_blocks_reused' | 'train_iterations' | 'train_evaluations' | 'predictions_behind_tail' |
-        'persistent_variance_products' (include/gpmpc.h)."""
+        'persistent_variance_products' | 'remove_downdates' | 'remove_refits' (include/gpmpc.h)."""
         v = ctypes.c_long(0)
         self.lib.check(self.lib.dll.gpmpc_get_counter(self.h, name.encode(), ctypes.byref(v)))
         return v.value
@@ -361,6 +362,15 @@ class Handle:
         self.selected, self.gain = sel[:kout.value].copy(), gain[:kout.value].copy()
         self.lib.check(rc)
         return self.selected, self.gain
+
+    def remove(self, idx):
+        """Remove the training points idx (distinct, in [0, N)); the rest keep their order (gpmpc_remove)."""
+        idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int32)
+        rc = self.lib.dll.gpmpc_remove(self.h, len(idx), idx.ctypes.data_as(ctypes.c_void_p))
+        n = ctypes.c_int(0)                 # the library is the authority on the size, whether the call succeeded or not
+        self.lib.dll.gpmpc_get_size(self.h, ctypes.byref(n), None, None)
+        self.N = n.value
+        self.lib.check(rc)
 
     def predict_jac(self, method, Z, Sigma=None):
         """mean[B,Ny], cov[B,Ny,Ny] ('ME'/'TA') and J[B,Ny,d] = d mean / d z from one pass."""

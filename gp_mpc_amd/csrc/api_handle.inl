@@ -34,6 +34,7 @@ struct gpmpc_gp {
     long n_var_persist = 0;                              // variance products through the persistent static-schedule kernel
     long n_fused = 0;                                    // gpmpc_fit_predict_mean_var calls that took the fused route
     long n_behind_tail = 0;                              // predictions that started next to a fit's tail (predict_behind_tail)
+    long n_remove_down = 0, n_remove_refit = 0;          // gpmpc_remove calls that downdated the factors / that refitted
     long train_iters = 0, train_evals = 0;              // of the last gpmpc_train_multistart (this rank's restarts)
     double train_flop = 0.0;                            // ... and its algorithmic matrix flops: N^3/3 per Cholesky, per L^-1, per K^-1 lower triangle
     int nll_last_a = -1;                                 // the training workspace holds the factors of this output ...
@@ -393,6 +394,8 @@ int gpmpc_get_counter(gpmpc_gp* h, const char* name, long* value) {
     else if (std::strcmp(name, "fused_fit_predicts") == 0) *value = h->n_fused;
     else if (std::strcmp(name, "train_gflop") == 0) *value = (long)(h->train_flop * 1e-9 + 0.5);
     else if (std::strcmp(name, "persistent_variance_products") == 0) *value = h->n_var_persist;
+    else if (std::strcmp(name, "remove_downdates") == 0) *value = h->n_remove_down;
+    else if (std::strcmp(name, "remove_refits") == 0) *value = h->n_remove_refit;
     else if (std::strcmp(name, "train_iterations") == 0) *value = h->train_iters;
     else if (std::strcmp(name, "train_evaluations") == 0) *value = h->train_evals;
     else if (std::strcmp(name, "workspace_blocks_reused") == 0 || std::strcmp(name, "workspace_blocks_fresh") == 0) {

@@ -149,6 +149,11 @@ extern "C" int gpmpc_set_tuning(const char* name, int value) {
         g_em_sens_chunk = value;
         return GPMPC_OK;
     }
+    if (std::strcmp(name, "remove_mode") == 0) {         // gpmpc_remove: 0 automatic, 1 always downdate, 2 always refit (-1 = default)
+        if (value < -1 || value > 2) return fail(GPMPC_EINVAL, "remove_mode must be -1 (default), 0, 1 or 2");
+        g_remove_mode = value;
+        return GPMPC_OK;
+    }
     if (std::strcmp(name, "fail_nll_after") == 0) {      // fault injection for the tests of the restart shard's failure paths
         if (value < 0) return fail(GPMPC_EINVAL, "fail_nll_after must be >= 0");
         static const bool testing = getenv("GPMPC_TESTING") && atoi(getenv("GPMPC_TESTING")) != 0;

@@ -3,6 +3,7 @@
 // The host code is split by concern into the api_*.inl files included below, in dependency order.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -27,6 +28,7 @@
 #include "gemm_f64_dma.hpp"
 #include "gp_kernels.hpp"
 #include "leaf64.hpp"
+#include "remove_kernels.hpp"
 #include "select_kernels.hpp"
 #include "train_native.hpp"
 #include "vargemm_persist.hpp"
@@ -40,6 +42,7 @@ using namespace gpmpc;
 #include "api_fit.inl"
 #include "api_predict.inl"
 #include "api_select.inl"
+#include "api_remove.inl"
 #include "api_rollout.inl"
 #include "api_train.inl"
 #include "api_lowlevel.inl"

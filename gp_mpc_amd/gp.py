@@ -423,6 +423,44 @@ class GP:
         self.__Y = np.vstack([self.__Y, Y_new])
         self.__N = self.__X.shape[0]
 
+    def remove_data(self, idx):
+        """Take the training rows `idx` (distinct indices into the current data) out of the model, keep the
+        hyper-parameters; the other rows keep their order.  The reference has nothing of the kind -- its only way to drop
+        data is `replace_data_all` (gp_class.py:553-626), a full recomputation; here the factors are downdated on the
+        device (`gpmpc_remove`, O(N^2 n)) -- same result to rounding."""
+        idx = np.asarray(idx).reshape(-1)
+        n0 = self.__N
+        try:
+            self._h.remove(idx)
+        finally:
+            if self._h.N == n0 - len(idx):                # (a refused call leaves the handle's size where it was)
+                keep = np.ones(n0, dtype=bool)
+                keep[idx] = False
+                self.__X, self.__Y = self.__X[keep], self.__Y[keep]
+                self.__N = self.__X.shape[0]
+
+    def update_data_window(self, X_new, Y_new, N_max):
+        """Sliding data window: afterwards the model holds the last `N_max` rows of vstack(X, X_new), in that order, with
+        the EXISTING hyper-parameters -- the fixed-budget form of `update_data_all` for a loop that keeps learning.  The
+        oldest rows go first (`gpmpc_remove`, smaller factors), then the new ones are appended (`gpmpc_append`); with
+        len(X_new) >= N_max it is `replace_data_all` on the last N_max new rows."""
+        X_new = np.array(X_new, dtype=np.float64).copy().reshape(-1, self.__Nx)
+        Y_new = np.array(Y_new, dtype=np.float64).copy().reshape(-1, self.__Ny)
+        N_max = int(N_max)
+        if N_max < 1:
+            raise ValueError('update_data_window: N_max must be >= 1')
+        if X_new.shape[0] >= N_max:
+            return self.replace_data_all(X_new[-N_max:], Y_new[-N_max:])
+        if X_new.shape[0] == 0:
+            drop = self.__N - N_max
+            if drop > 0:
+                self.remove_data(np.arange(drop))
+            return
+        drop = self.__N + X_new.shape[0] - N_max
+        if drop > 0:
+            self.remove_data(np.arange(drop))
+        self.update_data_all(X_new, Y_new)
+
     def replace_data_all(self, X_new, Y_new):
         """Replace the training data, keep the hyper-parameters (gp_class.py:553-626)."""
         X_new = np.array(X_new, dtype=np.float64).copy()

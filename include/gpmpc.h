@@ -172,6 +172,21 @@ int gpmpc_append(gpmpc_gp* h, int n, const double* Xnew, const double* Ynew, int
  * GPMPC_ENOTFIT without factors; GPMPC_EINVAL for bad sizes or NULLs (the handle stays usable). */
 int gpmpc_append_select(gpmpc_gp* h, int n, const double* Xcand, const double* Ycand, int k, double min_gain,
                         int* selected, double* gain, int* k_out, int* info);
+/* Remove n training points and update L, L^-1, alpha with the EXISTING hyper-parameters and the stored jitter: the model
+ * that gpmpc_fit gives on the remaining points (kept in their original order), to rounding, in O(N^2 n) instead of O(N^3).
+ * The reference can only replace all the data (GP.replace_data_all, gp_class.py:553-626: a full recomputation); together with
+ * gpmpc_append this keeps an online model at a fixed size.  idx[n]: HOST array of distinct indices in [0, N), any order,
+ * 1 <= n < N (at least one point stays).  GPMPC_EINVAL for duplicates, indices out of range, n <= 0, n >= N, NULL handle or
+ * idx (the handle stays usable, the model untouched); GPMPC_ENOTFIT without factors.  X, Y, N and the padded size follow; alpha
+ * is recomputed from the new L^-1 (stored mean parameters included), K^-1 is rebuilt lazily, as after gpmpc_append.  The new
+ * buffers are built beside the old ones and installed at the end: a HIP or allocation failure leaves the model unchanged.  A
+ * principal submatrix of a positive-definite matrix is positive definite: there is no `info` and no GPMPC_ENOTPD on the downdate.
+ * Method (remove_kernels.hpp): one Householder reflector per kept column from the first removed index on maps [L[S,S] L[S,R]] to
+ * [L' 0] and, from the left, [L^-1[S,S]; L^-1[R,S]] to L'^-1; 64 removed points per pass, two launches per 64-column panel;
+ * trailing indices leave the leading blocks of L and L^-1 bit for bit.  Where that cannot pay (small N, many points) the call
+ * refits on the remaining rows instead, with gpmpc_append's rollback; gpmpc_set_tuning("remove_mode", 0 automatic / 1 always
+ * downdate / 2 always refit / -1 default) overrides the choice, counters "remove_downdates" / "remove_refits" tell which ran. */
+int gpmpc_remove(gpmpc_gp* h, int n, const int* idx);
 
 /* Import a saved model (GP.load_model -> ctor branch gp_class.py:58-66): chol and hyper are
  * required; alpha == NULL recomputes it from Y; invK == NULL computes it lazily when a method
