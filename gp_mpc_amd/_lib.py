@@ -58,6 +58,7 @@ SIGNATURES = {
     'gpmpc_append': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
     'gpmpc_append_select': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp]),
     'gpmpc_remove': (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    'gpmpc_sparse_fitc': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
     'gpmpc_predict_mean_var': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
     'gpmpc_mean_jac': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
     'gpmpc_predict_sens': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -371,6 +372,24 @@ class Handle:
         self.lib.dll.gpmpc_get_size(self.h, ctypes.byref(n), None, None)
         self.N = n.value
         self.lib.check(rc)
+
+    def sparse_fitc(self, Xu, hyper=None):
+        """FITC model on the inducing points Xu[M, d] (standardised units) as a new, predict-only Handle of size M
+        (gpmpc_sparse_fitc).  hyper None: the hyper-parameters stored on this (fitted) model."""
+        Xu = _f64(Xu).reshape(-1, self.d)
+        M = Xu.shape[0]
+        if hyper is not None:
+            hyper = _f64(hyper).reshape(self.Ny, self.d + 2)
+        info = np.zeros(self.Ny, dtype=np.int32)
+        out = ctypes.c_void_p()
+        rc = self.lib.dll.gpmpc_sparse_fitc(self.h, _ptr(hyper), M, _ptr(Xu), info.ctypes.data_as(ctypes.c_void_p),
+                                            ctypes.byref(out))
+        self.info = info
+        self.lib.check(rc)
+        s = Handle.__new__(Handle)
+        s.lib, s.h, s.N, s.d, s.Ny = self.lib, out, M, self.d, self.Ny
+        s.device, s.device_mode, s.nh, s.info = self.device, False, self.d + 2, info
+        return s
 
     def predict_jac(self, method, Z, Sigma=None):
         """mean[B,Ny], cov[B,Ny,Ny] ('ME'/'TA') and J[B,Ny,d] = d mean / d z from one pass."""

@@ -263,15 +263,27 @@ struct Workspace {
     }
 };
 
-static int ws_alloc(Workspace& ws, int batch, int Np, int d) {
-    ws.batch = batch;
-    ws.Np = Np;
-    ws.d = d;
-    const size_t mb = (size_t)batch * Np * Np * sizeof(double);
+// The Np x Np blocks of a workspace (K, L, L^-1, the inverse's scratch).  gpmpc_create leaves them out -- a handle that only
+// carries data (the source of gpmpc_sparse_fitc at an N no exact fit is asked for) never pays for them -- and the first
+// fit / import allocates them here.
+static int ws_need_mats(Workspace& ws) {
+    if (ws.K) return GPMPC_OK;
+    const size_t mb = (size_t)ws.batch * ws.Np * ws.Np * sizeof(double);
     HIPCHK(block_alloc(&ws.K, mb));
     HIPCHK(block_alloc(&ws.L, mb));
     HIPCHK(block_alloc(&ws.Inv, mb));
-    HIPCHK(block_alloc(&ws.W, (size_t)batch * ws.wstride() * sizeof(double)));
+    HIPCHK(block_alloc(&ws.W, (size_t)ws.batch * ws.wstride() * sizeof(double)));
+    HIPCHK(hipMemset(ws.K, 0, mb));
+    HIPCHK(hipMemset(ws.L, 0, mb));
+    HIPCHK(hipMemset(ws.Inv, 0, mb));
+    return GPMPC_OK;
+}
+
+static int ws_alloc(Workspace& ws, int batch, int Np, int d, bool mats = true) {
+    ws.batch = batch;
+    ws.Np = Np;
+    ws.d = d;
+    if (mats) CHK(ws_need_mats(ws));
     HIPCHK(hipMalloc(&ws.Wl, (size_t)batch * Workspace::wl_stride() * sizeof(double)));
     HIPCHK(hipMalloc(&ws.w, (size_t)batch * Np * sizeof(double)));
     HIPCHK(hipMalloc(&ws.alpha, (size_t)batch * Np * sizeof(double)));
@@ -280,9 +292,6 @@ static int ws_alloc(Workspace& ws, int batch, int Np, int d) {
     HIPCHK(hipMalloc(&ws.nll, (size_t)batch * sizeof(double)));
     HIPCHK(hipMalloc(&ws.info, (size_t)batch * sizeof(int)));
     HIPCHK(hipMalloc(&ws.flags, (size_t)batch * chain_flag_count(Np / 64) * sizeof(int)));
-    HIPCHK(hipMemset(ws.K, 0, mb));
-    HIPCHK(hipMemset(ws.L, 0, mb));
-    HIPCHK(hipMemset(ws.Inv, 0, mb));
     HIPCHK(hipMemset(ws.alpha, 0, (size_t)batch * Np * sizeof(double)));
     HIPCHK(hipMemset(ws.w, 0, (size_t)batch * Np * sizeof(double)));
     // only factor_with_jitter writes these; gpmpc_set_factors -> gpmpc_append reads jitter without a fit in between

@@ -154,6 +154,7 @@ static int factor_with_jitter(gpmpc_gp* h, Workspace& ws, const double* hyper_ho
 static int fit_impl(gpmpc_gp* h, const double* hyper, int want_invK, int* info, const std::function<int()>* fused) {
     if (!h || !hyper) return fail(GPMPC_EINVAL, "NULL handle/hyper");
     HIPCHK(hipSetDevice(h->device));
+    CHK(ws_need_mats(h->ws));
     const int nh = h->nh();
     for (int a = 0; a < h->Ny; ++a)
         for (int k = 0; k < h->d + 2; ++k) {
@@ -220,6 +221,7 @@ static int fit_impl(gpmpc_gp* h, const double* hyper, int want_invK, int* info, 
 }
 
 extern "C" int gpmpc_fit(gpmpc_gp* h, const double* hyper, int want_invK, int* info) {
+    CHK(refuse_sparse(h, "gpmpc_fit"));
     return fit_impl(h, hyper, want_invK, info, nullptr);
 }
 
@@ -257,6 +259,7 @@ static int refresh_residual(gpmpc_gp* h) {
 
 extern "C" int gpmpc_append(gpmpc_gp* h, int n, const double* Xnew, const double* Ynew, int* info) {
     if (!h || n <= 0 || !Xnew || !Ynew) return fail(GPMPC_EINVAL, "NULL handle/data or n <= 0");
+    CHK(refuse_sparse(h, "gpmpc_append"));
     if (!h->fitted) return fail(GPMPC_ENOTFIT, "model has no factors (call gpmpc_fit or gpmpc_set_factors)");
     HIPCHK(hipSetDevice(h->device));
     alpha_ready(h);
@@ -456,7 +459,9 @@ extern "C" int gpmpc_get_factors(gpmpc_gp* h, double* hyper, double* chol, doubl
 extern "C" int gpmpc_set_factors(gpmpc_gp* h, const double* hyper, const double* chol, const double* alpha,
                                  const double* invK) {
     if (!h || !hyper || !chol) return fail(GPMPC_EINVAL, "hyper and chol are required");
+    CHK(refuse_sparse(h, "gpmpc_set_factors"));
     HIPCHK(hipSetDevice(h->device));
+    CHK(ws_need_mats(h->ws));
     alpha_ready(h);
     h->tail.armed = false;
     HIPCHK(hipStreamSynchronize(h->stream));

@@ -48,6 +48,7 @@ struct gpmpc_gp {
     int ptr_mode = GPMPC_PTR_HOST;
     int crow_mode = 0;
     bool fitted = false, have_invK = false;
+    bool sparse = false;                 // a FITC model built by gpmpc_sparse_fitc (api_sparse.inl): predict-only
     double *XT = nullptr, *Y = nullptr;  // [d][Np], [Ny][Np]
     Workspace ws;                        // model factors, batch = Ny
     Workspace tws;                       // training workspace, batch = 1 (lazy)
@@ -95,6 +96,13 @@ struct gpmpc_gp {
                    chain_mode >= 2 ? bulk_stream : nullptr, chain_mode >= 3 ? &tail : nullptr};
     }
 };
+
+// What changes data, hyper-parameters or factors is refused on a FITC handle: its (Xu, Yu, L, alpha, K^-1) are not the
+// factors of any kernel matrix, so nothing can be refitted or extended from them.
+static int refuse_sparse(const gpmpc_gp* h, const char* what) {
+    if (h && h->sparse) return fail(GPMPC_EINVAL, "%s: this handle is a FITC sparse model (gpmpc_sparse_fitc) and is predict-only", what);
+    return GPMPC_OK;
+}
 
 struct PhaseTimer : ProfScope {
     PhaseTimer(gpmpc_gp* h, int ph) : ProfScope(&h->prof, h->stream, ph) {}
@@ -235,7 +243,7 @@ static int create_impl(gpmpc_gp* h, const double* X, const double* Y) {
     HIPCHK(hipMalloc(&h->Y, yt.size() * sizeof(double)));
     HIPCHK(hipMemcpy(h->XT, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->Y, yt.data(), yt.size() * sizeof(double), hipMemcpyHostToDevice));
-    CHK(ws_alloc(h->ws, Ny, Np, d));
+    CHK(ws_alloc(h->ws, Ny, Np, d, false));     // (the N x N blocks come with the first fit / import: ws_need_mats)
     h->hyper.assign((size_t)Ny * (d + 2), 0.0);
     return GPMPC_OK;
 }
@@ -333,6 +341,7 @@ int gpmpc_get_size(const gpmpc_gp* h, int* N, int* d, int* Ny) {
 int gpmpc_set_mean_func(gpmpc_gp* h, int kind, int add_to_prediction) {
     if (!h) return fail(GPMPC_EINVAL, "NULL handle");
     if (kind < GPMPC_MEAN_ZERO || kind > GPMPC_MEAN_POLYNOMIAL) return fail(GPMPC_EINVAL, "No mean function with code %d", kind);
+    CHK(refuse_sparse(h, "gpmpc_set_mean_func"));
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->mean_kind = kind;

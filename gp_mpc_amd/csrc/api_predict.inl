@@ -354,6 +354,7 @@ extern "C" int gpmpc_predict_mean_var(gpmpc_gp* h, int B, const double* Z, doubl
 extern "C" int gpmpc_fit_predict_mean_var(gpmpc_gp* h, const double* hyper, int want_invK, int* info, int B, const double* Z,
                                           double* mean, double* var) {
     if (!h || !hyper) return fail(GPMPC_EINVAL, "NULL handle/hyper");
+    CHK(refuse_sparse(h, "gpmpc_fit_predict_mean_var"));
     if (B <= 0 || !Z) return fail(GPMPC_EINVAL, "bad B or NULL Z");
     if (!mean && !var) return fail(GPMPC_EINVAL, "both outputs NULL");
     static const bool fused_env = !(getenv("GPMPC_FUSED_FIT_PREDICT") && atoi(getenv("GPMPC_FUSED_FIT_PREDICT")) == 0);

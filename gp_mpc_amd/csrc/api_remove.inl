@@ -87,6 +87,7 @@ static int remove_pass(hipStream_t st, int Ny, const double* L0, const double* T
 
 extern "C" int gpmpc_remove(gpmpc_gp* h, int n, const int* idx) {
     if (!h || !idx) return fail(GPMPC_EINVAL, "NULL handle or idx");
+    CHK(refuse_sparse(h, "gpmpc_remove"));
     if (n <= 0 || n >= h->N) return fail(GPMPC_EINVAL, "remove: need 1 <= n < N (n = %d, N = %d)", n, h->N);
     std::vector<int> rem(idx, idx + n);
     std::sort(rem.begin(), rem.end());

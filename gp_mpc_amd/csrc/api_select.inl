@@ -68,6 +68,7 @@ static int select_greedy(gpmpc_gp* h, int n, const double* Xcand, int k, double 
 extern "C" int gpmpc_append_select(gpmpc_gp* h, int n, const double* Xcand, const double* Ycand, int k, double min_gain,
                                    int* selected, double* gain, int* k_out, int* info) {
     if (!h || !Xcand || !selected) return fail(GPMPC_EINVAL, "NULL handle, candidates or selected");
+    CHK(refuse_sparse(h, "gpmpc_append_select"));
     if (n <= 0 || k < 1 || k > n) return fail(GPMPC_EINVAL, "append_select: need 1 <= k <= n (k = %d, n = %d)", k, n);
     if (!(min_gain == min_gain)) return fail(GPMPC_EINVAL, "append_select: min_gain is NaN");
     if (!h->fitted) return fail(GPMPC_ENOTFIT, "model has no factors (call gpmpc_fit or gpmpc_set_factors)");

@@ -73,6 +73,7 @@ static int nll_grad_last(gpmpc_gp* h, int a, const double* hyper_row, double* gr
 
 extern "C" int gpmpc_nll(gpmpc_gp* h, int a, const double* hyper_row, double* nll, double* grad, int* jitter_out) {
     if (!h || !hyper_row || !nll || a < 0 || a >= h->Ny) return fail(GPMPC_EINVAL, "bad arguments");
+    CHK(refuse_sparse(h, "gpmpc_nll"));
     if (g_fail_nll_after.load(std::memory_order_relaxed) > 0 && g_fail_nll_after.fetch_sub(1) == 1)
         return fail(GPMPC_EHIP, "injected device failure (fail_nll_after)");
     HIPCHK(hipSetDevice(h->device));
@@ -528,7 +529,9 @@ extern "C" int gpmpc_train_multistart(gpmpc_gp* h, int nstart, const double* sta
                                       double* hyper_opt, double* obj, double* theta_all, int* info, int* status) {
     if (!h || nstart <= 0 || !starts || !lb || !ub || !hyper_opt) return fail(GPMPC_EINVAL, "NULL argument or nstart <= 0");
     if (world < 1 || rank < 0 || rank >= world) return fail(GPMPC_EINVAL, "bad rank %d / world %d", rank, world);
+    CHK(refuse_sparse(h, "gpmpc_train_multistart"));
     HIPCHK(hipSetDevice(h->device));
+    CHK(ws_need_mats(h->ws));     // (the fit at the optimum needs them: taken before the search sizes its batches by the free memory)
     const int Ny = h->Ny, nh = h->nh(), d = h->d, row = nh + 1;
     const double inf = std::numeric_limits<double>::infinity();
     if (max_iter <= 0) max_iter = 200;

@@ -25,6 +25,7 @@
 #include "chol_chain.hpp"
 #include "chol_worker.hpp"
 #include "em_kernels.hpp"
+#include "fitc_kernels.hpp"
 #include "gemm_f64_dma.hpp"
 #include "gp_kernels.hpp"
 #include "leaf64.hpp"
@@ -43,6 +44,7 @@ using namespace gpmpc;
 #include "api_predict.inl"
 #include "api_select.inl"
 #include "api_remove.inl"
+#include "api_sparse.inl"
 #include "api_rollout.inl"
 #include "api_train.inl"
 #include "api_lowlevel.inl"

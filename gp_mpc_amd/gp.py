@@ -60,6 +60,7 @@ class GP:
         self.__normalize = normalize
         self._predict_adds_mean = bool(predict_adds_mean)
         self._h = None
+        self._sparse = False                  # True on what GP.sparse returns: a FITC model, predict-only
         self._check_mean_func(mean_func)
 
         if meta is not None:
@@ -100,6 +101,11 @@ class GP:
         if mean_func not in ('zero', 'const', 'linear', 'polynomial'):
             raise NameError('No mean function called: ' + str(mean_func))      # gp_functions.py:67
 
+    def _refuse_sparse(self, what):
+        if self._sparse:
+            raise RuntimeError(what + ': this object is a FITC sparse model (GP.sparse) and is predict-only; '
+                               'change the data or the hyper-parameters on the full model and call sparse() again')
+
     def _new_handle(self):
         if self._h is not None:
             self._h.close()
@@ -125,6 +131,7 @@ class GP:
         (`gp_mpc_amd.train.train_gp`) that evaluates the NLL and its analytic gradient on the GPU;
         `optimize_nummeric` selects the reference's bound/initialisation convention of the
         corresponding path (True: optimize.py:434-449, False: optimize.py:207-229)."""
+        self._refuse_sparse('optimize')
         self._check_mean_func(mean_func)
         self.__mean_func = mean_func
         self.__normalize = normalize
@@ -373,6 +380,7 @@ class GP:
         """The reference documents its incremental update as not working (gp_class.py:384-471:
         argmin for 'max variance' :421, norm instead of norm^2 :443); `update_data_select` does what it set out to
         do, `update_data_all` appends everything."""
+        self._refuse_sparse('update_data')
         raise NotImplementedError('update_data is broken in the reference (gp_class.py:384-471); '
                                   'use update_data_select (the N_new most informative points), '
                                   'update_data_all / replace_data_all')
@@ -386,6 +394,7 @@ class GP:
         Selection stops early when the best score (standardised units) falls below `min_gain` (> 0).  The taken rows are
         appended like `update_data_all` does; `Y_new=None` only selects (experiment design) and changes nothing.
         Returns (indices into X_new in pick order, their scores when picked)."""
+        self._refuse_sparse('update_data_select')
         X_new = np.array(X_new, dtype=np.float64).copy().reshape(-1, self.__Nx)
         if Y_new is not None:
             Y_new = np.array(Y_new, dtype=np.float64).copy().reshape(-1, self.__Ny)
@@ -413,6 +422,7 @@ class GP:
         """Append all new observations and bring chol/alpha/invK up to date with the EXISTING
         hyper-parameters (gp_class.py:474-550).  The reference recomputes everything, O(N^3); here
         the factors are extended on the device (`gpmpc_append`, O(N^2 n)) -- same result to rounding."""
+        self._refuse_sparse('update_data_all')
         X_new = np.array(X_new, dtype=np.float64).copy().reshape(-1, self.__Nx)
         Y_new = np.array(Y_new, dtype=np.float64).copy().reshape(-1, self.__Ny)
         if self.__normalize:
@@ -428,6 +438,7 @@ class GP:
         hyper-parameters; the other rows keep their order.  The reference has nothing of the kind -- its only way to drop
         data is `replace_data_all` (gp_class.py:553-626), a full recomputation; here the factors are downdated on the
         device (`gpmpc_remove`, O(N^2 n)) -- same result to rounding."""
+        self._refuse_sparse('remove_data')
         idx = np.asarray(idx).reshape(-1)
         n0 = self.__N
         try:
@@ -444,6 +455,7 @@ class GP:
         the EXISTING hyper-parameters -- the fixed-budget form of `update_data_all` for a loop that keeps learning.  The
         oldest rows go first (`gpmpc_remove`, smaller factors), then the new ones are appended (`gpmpc_append`); with
         len(X_new) >= N_max it is `replace_data_all` on the last N_max new rows."""
+        self._refuse_sparse('update_data_window')
         X_new = np.array(X_new, dtype=np.float64).copy().reshape(-1, self.__Nx)
         Y_new = np.array(Y_new, dtype=np.float64).copy().reshape(-1, self.__Ny)
         N_max = int(N_max)
@@ -463,6 +475,7 @@ class GP:
 
     def replace_data_all(self, X_new, Y_new):
         """Replace the training data, keep the hyper-parameters (gp_class.py:553-626)."""
+        self._refuse_sparse('replace_data_all')
         X_new = np.array(X_new, dtype=np.float64).copy()
         Y_new = np.array(Y_new, dtype=np.float64).copy()
         if self.__normalize:
@@ -512,9 +525,73 @@ class GP:
     def noise_variance(self):
         return self.__hyper_noise_variance                                      # gp_class.py:675-678
 
-    def sparse(self, M):
-        """FITC stub, empty in the reference too (gp_class.py:682-689)."""
-        return None
+    def sparse_default_inducing(self, M):
+        """Indices of the M training rows `sparse` takes when no inducing points are given: row 0, then the greedy
+        max-variance choice among the others with the model's hyper-parameters -- a seed model on row 0 and
+        `append_select(X[1:], None, k=M-1)` on it (selection only): the pivoted-Cholesky choice, lowest index among ties."""
+        M = int(M)
+        if M < 1 or M > self.__N:
+            raise ValueError('sparse: need 1 <= M <= N (M = %d, N = %d)' % (M, self.__N))
+        if M == 1:
+            return np.zeros(1, dtype=np.int64)
+        seed = _lib.Handle(self._lib, self.__X[:1], self.__Y[:1], device=self._device)
+        try:
+            seed.fit(self.__hyper[:, :self.__Nx + 2])
+            try:
+                sel, _ = seed.append_select(self.__X[1:], None, M - 1)
+            except _lib.GpmpcError as e:
+                if 'single-chunk limit' in str(e):
+                    raise ValueError('sparse: N - 1 = %d candidates exceed the single-chunk limit of the greedy '
+                                     'selection; pass `inducing` (indices or points)' % (self.__N - 1)) from e
+                raise
+        finally:
+            seed.close()
+        if len(sel) != M - 1:
+            raise ValueError('sparse: the greedy selection returned %d of %d points; pass `inducing`' % (len(sel), M - 1))
+        return np.concatenate([[0], np.asarray(sel, dtype=np.int64) + 1])
+
+    def sparse(self, M, inducing=None):
+        """Fully Independent Training Conditional (FITC) model on M inducing points: what the reference names and leaves
+        empty (gp_class.py:681-689, "reduce the model size from N to M").  Returns a NEW GP object whose handle is the
+        sparse one (`gpmpc_sparse_fitc`): the same normalisation constants, hyper-parameters, method and bounds, X / Y
+        = the inducing points Xu and the pseudo-targets Yu; every prediction costs O(M^2) instead of O(N^2).  `predict*`,
+        `covar`, `discrete_linearize`, `jacobian`, `rollout*`, `validate` and `save_model` work on it (the saved file is
+        the reference's format: its `load_model` predicts FITC from it); what changes data or hyper-parameters raises.
+        inducing: an int array of M training indices, an (M x Nx) array of raw points (standardised here), or None =
+        `sparse_default_inducing(M)`."""
+        if self.__mean_func != 'zero':
+            raise ValueError("sparse: FITC is built for the 'zero' mean function only")
+        self._refuse_sparse('sparse')
+        M = int(M)
+        if M < 1 or M > self.__N:
+            raise ValueError('sparse: need 1 <= M <= N (M = %d, N = %d)' % (M, self.__N))
+        if inducing is None:
+            Xu = self.__X[self.sparse_default_inducing(M)]
+        else:
+            inducing = np.asarray(inducing)
+            if inducing.dtype.kind in 'iu':
+                idx = inducing.reshape(-1)
+                if len(idx) != M or idx.min() < 0 or idx.max() >= self.__N:
+                    raise ValueError('sparse: `inducing` must hold M = %d training indices in [0, %d)' % (M, self.__N))
+                Xu = self.__X[idx]
+            else:
+                Xu = np.array(inducing, dtype=np.float64).reshape(-1, self.__Nx)
+                if Xu.shape[0] != M:
+                    raise ValueError('sparse: `inducing` holds %d points, M = %d' % (Xu.shape[0], M))
+                if self.__normalize:
+                    Xu = self.standardize(Xu, self.__meanZ, self.__stdZ)
+        Xu = np.ascontiguousarray(Xu, dtype=np.float64)
+        hs = self._h.sparse_fitc(Xu, self.__hyper[:, :self.__Nx + 2])
+        f = hs.get_factors(chol=True, alpha=True, invK=False)
+        Yu = np.stack([f['chol'][a] @ (f['chol'][a].T @ f['alpha'][a]) for a in range(self.__Ny)], axis=1)
+        g = object.__new__(GP)
+        for k, v in self.__dict__.items():
+            if k not in ('_h', 'train_info'):
+                g.__dict__[k] = v.copy() if isinstance(v, np.ndarray) else v
+        g._h = hs
+        g._sparse = True
+        g.__X, g.__Y, g.__N = Xu.copy(), Yu, M
+        return g
 
     # ------------------------------------------------------------------ persistence (gp_class.py:693-743)
     def _to_dict(self, as_arrays=False):

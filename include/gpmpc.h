@@ -188,6 +188,33 @@ int gpmpc_append_select(gpmpc_gp* h, int n, const double* Xcand, const double* Y
  * downdate / 2 always refit / -1 default) overrides the choice, counters "remove_downdates" / "remove_refits" tell which ran. */
 int gpmpc_remove(gpmpc_gp* h, int n, const int* idx);
 
+/* FITC sparse model (what GP.sparse, gp_class.py:681-689, names and leaves empty: "Use Fully Independent Training Conditional
+ * (FITC) ... reduce the model size from N to M"): from the N training points of `h` and M inducing points Xu[M x d] (HOST
+ * pointer, standardised units, 1 <= M <= N) a NEW handle *out of size (M, d, Ny) on h's device; `h` is untouched.
+ * hyper[Ny x (d+2)]: the hyper-parameters to build with; `h` then needs no factors and the call allocates nothing of size
+ * N x N (gpmpc_create does not either: the N x N blocks of a handle come with its first fit / import), so a source may hold
+ * far more points than an exact fit can factor.  hyper == NULL: the ones stored on `h` (GPMPC_ENOTFIT without factors).
+ * The source's prior mean must be 'zero' (GPMPC_EINVAL otherwise).  Per output a with (ell, sf, sn):
+ *   Kuu = k(Xu,Xu) + 1e-6 sf^2 I (GPML's inducing jitter), Luu = chol(Kuu) -- info[a] follows the rule of gpmpc_fit (may be NULL);
+ *   V = Luu^-1 k(Xu,X);  lambda_i = max(sf^2 - sum_m V_mi^2, 0) + sn^2;  Vs = V Lambda^-1/2;  B = I + Vs Vs^T;  r = Vs Lambda^-1/2 y;
+ *   alpha_u = Luu^-T B^-1 r;  P = Luu^-T (I - B^-1) Luu^-1  (= Kuu^-1 - Sigma^-1, Quinonero-Candela & Rasmussen 2005 eq. 24).
+ * The FITC predictor mean = k(z,Xu) alpha_u, var = sf^2 - k(z,Xu) P k(Xu,z) has the form of an exact GP on the inducing points
+ * with K^-1 -> P, and so have the exact-moment formulas (as in PILCO).  The new handle therefore carries X = Xu, the given
+ * hyper rows, alpha = alpha_u, K^-1 = P, L^-1 = W and L = W^-1 for the lower triangular W with W^T W = P (the Cholesky factor of
+ * the index-reversed P, transposed and reversed back), Y = Yu = L L^T alpha_u, stored jitter 0 -- and EVERY entry point that
+ * predicts (the predict family, sensitivities, gpmpc_covar, all five methods, the roll-outs) evaluates FITC on it unchanged;
+ * gpmpc_get_factors exports it in the reference's save_model layout.  A Cholesky of B or of the reversed P that fails:
+ * GPMPC_ENOTPD, info[a] = -(pivot), *out = NULL; every other error leaves *out = NULL and `h` usable as well.
+ * The sparse handle is predict-only: gpmpc_fit, gpmpc_fit_predict_mean_var, gpmpc_append, gpmpc_append_select, gpmpc_remove,
+ * gpmpc_nll, gpmpc_train_multistart, gpmpc_set_mean_func and gpmpc_set_factors return GPMPC_EINVAL on it (the handle stays
+ * usable); it cannot be the source of another gpmpc_sparse_fitc.
+ * Work: the training points are visited in chunks of the predict family's size (gpmpc_set_tuning "predict_chunk"); per chunk
+ * the cross-covariances, one product with Luu^-1 and the symmetric rank update B += Vs Vs^T on the fp64 matrix cores
+ * (fitc_kernels.hpp): O(N M^2); then an O(M^3) tail.  Nothing N-sized goes to the host.  The new handle inherits the
+ * source's profiling switch and mask; its GPMPC_PH_GRAM / _FACTOR brackets then hold the fit of Kuu, GPMPC_PH_VARGEMM the
+ * rank updates. */
+int gpmpc_sparse_fitc(gpmpc_gp* h, const double* hyper, int M, const double* Xu, int* info, gpmpc_gp** out);
+
 /* Import a saved model (GP.load_model -> ctor branch gp_class.py:58-66): chol and hyper are
  * required; alpha == NULL recomputes it from Y; invK == NULL computes it lazily when a method
  * needs it.  L^-1 (the predict operand) is rebuilt on the device. */
