@@ -556,7 +556,16 @@ class Handle:
 
     # -- raw device-pointer entry points (device pointer mode)
     def predict_mean_var_dev(self, B, z_ptr, mean_ptr, var_ptr):
+        """gpmpc_predict_mean_var on raw pointers (or arrays, in host mode); mean_ptr or var_ptr may be None."""
         self.lib.check(self.lib.dll.gpmpc_predict_mean_var(self.h, B, _ptr(z_ptr), _ptr(mean_ptr), _ptr(var_ptr)))
+
+    def predict_sens_dev(self, B, z_ptr, mean_ptr, var_ptr, J_ptr, Hm_ptr, dvar_ptr):
+        """gpmpc_predict_sens on raw pointers; any output may be None."""
+        self.lib.check(self.lib.dll.gpmpc_predict_sens(self.h, B, _ptr(z_ptr), _ptr(mean_ptr), _ptr(var_ptr), _ptr(J_ptr),
+                                                       _ptr(Hm_ptr), _ptr(dvar_ptr)))
+
+    def covar_dev(self, n, x_ptr, covar_ptr):
+        self.lib.check(self.lib.dll.gpmpc_covar(self.h, n, _ptr(x_ptr), _ptr(covar_ptr)))
 
     def fit_predict_mean_var_dev(self, hyper, B, z_ptr, mean_ptr, var_ptr, want_invK=False):
         """gpmpc_fit + gpmpc_predict_mean_var as ONE call with device pointers (the fused route of include/gpmpc.h)."""

@@ -30,6 +30,27 @@ static int fail(int code, const char* fmt, ...) {
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// Device scratch of one call: take<T>(count) is one hipMalloc, the destructor frees whatever was handed out -- on every way
+// out of the call.  A failed take returns nullptr, is kept in `status` (HIPCHK it after a group of takes) and stops the rest.
+struct DevArena {
+    std::vector<void*> blocks;
+    hipError_t status = hipSuccess;
+    DevArena() = default;
+    DevArena(const DevArena&) = delete;
+    DevArena& operator=(const DevArena&) = delete;
+    ~DevArena() {
+        for (void* p : blocks) hipFree(p);
+    }
+    template <class T>
+    T* take(size_t count) {
+        void* p = nullptr;
+        if (status == hipSuccess) status = hipMalloc(&p, count * sizeof(T));
+        if (status != hipSuccess) return nullptr;
+        blocks.push_back(p);
+        return (T*)p;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------
 // device bring-up + fp64 MFMA self-test
 // ------------------------------------------------------------------------------------------------
@@ -120,7 +141,7 @@ static int ensure_device(int device) {
             return fail(GPMPC_EHIP, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
         g_cu_count[device] = prop.multiProcessorCount;
 #else
-        g_cu_count[device] = getenv("GPMPC_EMU_CUS") ? atoi(getenv("GPMPC_EMU_CUS")) : 8;
+        g_cu_count[device] = env_int("GPMPC_EMU_CUS", 8);
 #endif
         if (!g_exp_tab[device]) {                               // 2^(j / 2048), correctly rounded (exp_tab, gp_kernels.hpp)
             std::vector<double> tab(EXPT_N);

@@ -10,6 +10,10 @@ static GemmP gemm_base(const Ctx& cx) {
 }
 
 static int g_vargemm_persist = -1;  // gpmpc_set_tuning("vargemm_persist", 0 / 1 / 2): dispatcher order / static schedule / ... at any size; -1: GPMPC_VARGEMM_PERSIST or default
+static int vargemm_persist_mode() {
+    static const int persist_env = env_int("GPMPC_VARGEMM_PERSIST", 1);
+    return g_vargemm_persist >= 0 ? g_vargemm_persist : persist_env;
+}
 static int g_worker_courier = -1;   // gpmpc_set_tuning("worker_courier", 0 / 1): tile owners only / with the courier; -1: GPMPC_COURIER or default
 
 // Fit factorisation = right-looking blocked Cholesky (NB = 64) + level-by-level batched triangular
@@ -172,11 +176,11 @@ static long long* g_chain_trace = nullptr;   // developer aid: GPMPC_CHAIN_TRACE
 // the chain kernel's publications as write-through stores + flag, no L2 write-back (wg_sync.hpp; GPMPC_CHAIN_WT=0: release fence)
 static int g_handoff_wt = -1;   // gpmpc_set_tuning("handoff_write_through", 0 / 1): both kernels; -1: GPMPC_CHAIN_WT / GPMPC_WORKER_WT or default
 static int chain_wt_publish() {
-    static const int v = getenv("GPMPC_CHAIN_WT") ? atoi(getenv("GPMPC_CHAIN_WT")) : 1;
+    static const int v = env_int("GPMPC_CHAIN_WT", 1);
     return g_handoff_wt >= 0 ? g_handoff_wt : v;
 }
 static int worker_wt_publish() {   // the same for the tile-owner workers and the courier (GPMPC_WORKER_WT)
-    static const int v = getenv("GPMPC_WORKER_WT") ? atoi(getenv("GPMPC_WORKER_WT")) : 1;
+    static const int v = env_int("GPMPC_WORKER_WT", 1);
     return g_handoff_wt >= 0 ? g_handoff_wt : v;
 }
 // Block columns per super-panel (GPMPC_TWOLEVEL=<n> pins it; 0 / 1 = off).  A function of the matrix size ONLY (a matrix's bits
@@ -186,11 +190,11 @@ static int worker_wt_publish() {   // the same for the tile-owner workers and th
 // 42.8 / 45.2 ms; N = 4096, 64 restarts: 99.4 / 102.9 / 101.7 / 104.1 / 92.7 restarts/s.
 static int twolevel_width(int Np) {
 #ifdef GPMPC_EMULATED
-    static const int w = getenv("GPMPC_TWOLEVEL") ? atoi(getenv("GPMPC_TWOLEVEL")) : 2;
+    static const int w = env_int("GPMPC_TWOLEVEL", 2);
     (void)Np;
     return w;
 #else
-    static const int w = getenv("GPMPC_TWOLEVEL") ? atoi(getenv("GPMPC_TWOLEVEL")) : -1;
+    static const int w = env_int("GPMPC_TWOLEVEL", -1);
     if (w >= 0) return w;
     const int nb = Np / 64;
     return nb > 64 ? 10 : nb >= 28 ? 14 : 8;
@@ -248,7 +252,7 @@ static bool factor_twolevel(const Ctx& cx, Workspace& ws, int spin_limit, int W,
     int* leafdone = ws.flags + 1;
     int* pan1 = ws.flags + 1 + nb;
     int* tdone = ws.flags + 1 + 2 * nb;
-    static const bool blocked_env = !(getenv("GPMPC_TWOLEVEL_BLOCKED") && atoi(getenv("GPMPC_TWOLEVEL_BLOCKED")) == 0);
+    static const bool blocked_env = env_int("GPMPC_TWOLEVEL_BLOCKED", 1) != 0;
     const int nsp = (nb + W - 1) / W;
     const bool blocked = blocked_env && ws.Wl && (long)(32 * W) * (32 * W) <= ws.wl_stride() && cx.seg && cx.n_seg >= 5 * nsp + 4;
     // The inverse follows panel by panel on the third queue -- right-looking blocked inversion of the row panels
@@ -269,7 +273,7 @@ static bool factor_twolevel(const Ctx& cx, Workspace& ws, int spin_limit, int W,
     // what the chain needs next) and B(s) = everything right of them (fourth queue, low priority), so that B(s) overlaps
     // the latency-bound factorisation of super-panel s+1.  Order on shared tiles: A(s) after B(s-1) (event), B(s) after
     // the panels of s (event) and after B(s-1) (queue order).
-    static const bool lookahead_on = !(getenv("GPMPC_LOOKAHEAD") && atoi(getenv("GPMPC_LOOKAHEAD")) == 0);
+    static const bool lookahead_on = env_int("GPMPC_LOOKAHEAD", 1) != 0;
     const bool lookahead = lookahead_on && cx.bulk && cx.seg && cx.n_seg >= 5 * nsp + 4;
     hipEvent_t evB_prev = nullptr;
     if (lookahead) {
@@ -372,7 +376,7 @@ static bool factor_twolevel(const Ctx& cx, Workspace& ws, int spin_limit, int W,
                 // 4096^2: 1.2 ms between the chain launch and its first leaf, per super-panel).  So B(s) starts only once that
                 // chain is resident -- its first leaf is out -- i.e. behind A(s) instead of next to it; what it then overlaps
                 // is the latency-bound part of super-panel s+1 (chain, diagonal-block inverse), which is the point.
-                static const bool gate_bulk = !(getenv("GPMPC_GATE_BULK") && atoi(getenv("GPMPC_GATE_BULK")) == 0);
+                static const bool gate_bulk = env_int("GPMPC_GATE_BULK", 1) != 0;
                 if (gate_bulk)
                     hipLaunchKernelGGL(flag_gate_kernel, dim3(ws.batch), dim3(64), 0, cx.bulk, ws.flags, (long)nf, 1 + k1, 1, -1, 0,
                                        spin_limit);
@@ -426,11 +430,11 @@ static bool factor_chain(const Ctx& cx, Workspace& ws, int spin_limit, bool flag
     int NW = ws.batch == 1 && !cx.no_workers ? cx.workers - cx.workers / 8 : 0;
     // (tuning aid) GPMPC_NW1=<n>: workgroups of the first worker launch instead of 7 per shader engine -- beyond that a
     // workgroup may have to wait for the chain's engine (see above): the hand-off time-out and its fallback catch that
-    static const int nw1_env = getenv("GPMPC_NW1") ? atoi(getenv("GPMPC_NW1")) : 0;
+    static const int nw1_env = env_int("GPMPC_NW1", 0);
     if (NW > 0 && nw1_env > 0) NW = std::min(nw1_env, cx.workers - 1);
     // the last workgroup of every worker launch is the chain's courier (chol_worker.hpp), no tile owner; GPMPC_COURIER=0:
     // tile owners only (r03 A/B on one box: factor 1.675 -> 1.630 ms at C2 with the courier)
-    static const bool worker_courier_env = !(getenv("GPMPC_COURIER") && atoi(getenv("GPMPC_COURIER")) == 0);
+    static const bool worker_courier_env = env_int("GPMPC_COURIER", 1) != 0;
     const bool worker_courier = g_worker_courier >= 0 ? g_worker_courier != 0 : worker_courier_env;   // (gpmpc_set_tuning("worker_courier", ..))
     const int ncour = worker_courier ? 1 : 0;
     const int worker_maxt = worker_courier ? WORKER_MAXT_COURIER : WORKER_MAXT;
@@ -445,7 +449,7 @@ static bool factor_chain(const Ctx& cx, Workspace& ws, int spin_limit, bool flag
         // (value only: L and the diagonal blocks' inverses suffice -- but only the blocked super-panels leave those behind)
         const int nsp = (nb + twolevel_W - 1) / twolevel_W;
         const bool can_skip = cx.value_only && ws.Wl && (long)(32 * twolevel_W) * (32 * twolevel_W) <= ws.wl_stride() &&
-                              cx.n_seg >= 5 * nsp + 4 && !(getenv("GPMPC_TWOLEVEL_BLOCKED") && atoi(getenv("GPMPC_TWOLEVEL_BLOCKED")) == 0);
+                              cx.n_seg >= 5 * nsp + 4 && env_int("GPMPC_TWOLEVEL_BLOCKED", 1) != 0;
         return factor_twolevel(cx, ws, spin_limit, twolevel_W, !can_skip);
     }
     // Worker launches and the row-panel schedule of the inverse.  The workers run as up to three launches
@@ -463,11 +467,11 @@ static bool factor_chain(const Ctx& cx, Workspace& ws, int spin_limit, bool flag
     int s_top = 64;                                         // rows of the left child of the inverse tree's root
     while (2 * s_top < Np) s_top *= 2;
     if (s_top >= 256 && Np - s_top < s_top / 4) s_top /= 2;   // (Np a little above a power of two: not "everything, then a sliver")
-    static const bool split_ok = !(getenv("GPMPC_WORKER_SPLIT") && atoi(getenv("GPMPC_WORKER_SPLIT")) == 0);
-    static const int max_launches = getenv("GPMPC_MAX_LAUNCHES") ? atoi(getenv("GPMPC_MAX_LAUNCHES")) : 3;
-    static const int nw2_env = getenv("GPMPC_NW2") ? atoi(getenv("GPMPC_NW2")) : 0;   // (tuning aids)
-    static const int nw3_env = getenv("GPMPC_NW3") ? atoi(getenv("GPMPC_NW3")) : 0;
-    static const int nw4_env = getenv("GPMPC_NW4") ? atoi(getenv("GPMPC_NW4")) : 0;
+    static const bool split_ok = env_int("GPMPC_WORKER_SPLIT", 1) != 0;
+    static const int max_launches = env_int("GPMPC_MAX_LAUNCHES", 3);
+    static const int nw2_env = env_int("GPMPC_NW2", 0);   // (tuning aids)
+    static const int nw3_env = env_int("GPMPC_NW3", 0);
+    static const int nw4_env = env_int("GPMPC_NW4", 0);
     // second launch: 96 of 256 CUs, <= 6 tiles per worker at Np = 4096 (measured: 64 / 96 / 128 / 160 / 192 workers ->
     // 2.44 / 2.40 / 2.43 / 2.53 / 2.61 ms; with the DMA-staged workers 64 .. 160 are within 1 %)
     const int nw_rule[4] = {NW, nw2_env > 0 ? nw2_env : std::max(1, cx.workers * 3 / 8),
@@ -477,7 +481,7 @@ static bool factor_chain(const Ctx& cx, Workspace& ws, int spin_limit, bool flag
     long wofs[5] = {0, 0, 0, 0, 0};                         // S_j of panel j (1 <= j < L) inside ws.W, ld = r[j]
     if (use_workers && split_ok && cx.aux && cx.seg) {
         long wo = ws.hw() * ws.hw();
-        static const int cut1 = getenv("GPMPC_CUT1") ? atoi(getenv("GPMPC_CUT1")) : 0;   // (tuning aid: block of the first cut)
+        static const int cut1 = env_int("GPMPC_CUT1", 0);   // (tuning aid: block of the first cut)
         int start = (cut1 > 0 && 64 * cut1 < Np) ? 64 * cut1 : s_top;
         while (L < 4 && L < max_launches && L + 1 <= cx.n_seg - 1) {
             const int a = start - r[L - 1];                 // rows of the panel the new cut closes
@@ -489,7 +493,7 @@ static bool factor_chain(const Ctx& cx, Workspace& ws, int spin_limit, bool flag
             int nxt = 64;                                   // next cut: the left child of what remains
             while (2 * nxt < Np - start) nxt *= 2;
             if (nxt >= 256 && Np - start - nxt < nxt / 4) nxt /= 2;
-            static const int cut2 = getenv("GPMPC_CUT2") ? atoi(getenv("GPMPC_CUT2")) : 0;   // (tuning aid: block of the second cut)
+            static const int cut2 = env_int("GPMPC_CUT2", 0);   // (tuning aid: block of the second cut)
             if (L == 2 && cut2 > 0 && 64 * cut2 > start && 64 * cut2 < Np) nxt = 64 * cut2 - start;
             start += nxt;
             if (start >= Np) break;
@@ -520,11 +524,11 @@ static bool factor_chain(const Ctx& cx, Workspace& ws, int spin_limit, bool flag
     // leafdone[k] together with pan1[k] (one release less on the chain's path; r01-r02 default next to workers) or on its own
     // right behind the leaf: since the courier and the workers' look-ahead start from inv_kk, the early publication wins
     // (r03 A/B: chain 1.310 -> 1.302 ms).  GPMPC_MERGE_PUBLISH=1: the old way.
-    static const bool merge_publish = getenv("GPMPC_MERGE_PUBLISH") && atoi(getenv("GPMPC_MERGE_PUBLISH")) != 0;
+    static const bool merge_publish = env_int("GPMPC_MERGE_PUBLISH", 0) != 0;
     const int wt_publish = chain_wt_publish();
-    static const int late_polls = getenv("GPMPC_LATE_POLLS") ? atoi(getenv("GPMPC_LATE_POLLS")) : 3;   // (tuning aid, chol_chain.hpp land())
+    static const int late_polls = env_int("GPMPC_LATE_POLLS", 3);   // (tuning aid, chol_chain.hpp land())
     // leafdone[k] behind the panel row's products in prefetched steps (chol_chain.hpp); GPMPC_CHAIN_DEFER_PUBLISH=0: in front, as r04
-    static const bool defer_publish = !(getenv("GPMPC_CHAIN_DEFER_PUBLISH") && atoi(getenv("GPMPC_CHAIN_DEFER_PUBLISH")) == 0);
+    static const bool defer_publish = env_int("GPMPC_CHAIN_DEFER_PUBLISH", 1) != 0;
     {   // the chain kernel ends with the last leaf, i.e. when L is complete: its duration is the Cholesky's
         ProfScope t(cx.prof, cx.stream, GPMPC_PH_CHAIN);
         hipLaunchKernelGGL(chol_chain_kernel, dim3(1, 1, ws.batch), dim3(256), CHAIN_LDS_BYTES, cx.stream, (const double*)ws.K,
@@ -533,12 +537,12 @@ static bool factor_chain(const Ctx& cx, Workspace& ws, int spin_limit, bool flag
     }
     // Early status (below): ev_chain marks the END OF THE CHAIN KERNEL, so it is recorded here, while that kernel is the main
     // queue's last entry (GPMPC_EV_CHAIN_LATE=1, tuning aid: behind the join with the workers' queue as r04 had it).
-    static const bool ev_chain_late = getenv("GPMPC_EV_CHAIN_LATE") && atoi(getenv("GPMPC_EV_CHAIN_LATE")) != 0;
+    static const bool ev_chain_late = env_int("GPMPC_EV_CHAIN_LATE", 0) != 0;
     const bool early_status = cx.tail && cx.tail->want_early && use_workers && split;
     if (early_status && !ev_chain_late) hipEventRecord(TailState::get(cx.tail->ev_chain), cx.stream);
     static const bool verbose = getenv("GPMPC_VERBOSE") != nullptr;
     // (tuning aid) GPMPC_WORKER_LOOKAHEAD=0: the workers turn a panel tile into L(i,k) only at the top of step k
-    static const bool worker_lookahead = !(getenv("GPMPC_WORKER_LOOKAHEAD") && atoi(getenv("GPMPC_WORKER_LOOKAHEAD")) == 0);
+    static const bool worker_lookahead = env_int("GPMPC_WORKER_LOOKAHEAD", 1) != 0;
     if (verbose)
         fprintf(stderr, "gpmpc: factor Np=%d batch=%d: chain kernel + %s (%d launch%s), inverse %s\n", Np, ws.batch,
                 use_workers ? "tile-owner workers" : "GEMM launches", use_workers ? L : 0, L == 1 ? "" : "es",
@@ -590,7 +594,7 @@ static bool factor_chain(const Ctx& cx, Workspace& ws, int spin_limit, bool flag
             // the inverse queue when launch i ends (r03 timeline: they ran until 0.19 ms after launch 2's end): they go to
             // a queue of their own from the second panel on (the low-priority one: a HIGH-priority queue for them made every
             // launch 5 x slower and the fit 2.67 ms), the products wait for them through an event.
-            static const bool trtri_own_queue = !(getenv("GPMPC_TRTRI_QUEUE") && atoi(getenv("GPMPC_TRTRI_QUEUE")) == 0);
+            static const bool trtri_own_queue = env_int("GPMPC_TRTRI_QUEUE", 1) != 0;
             hipStream_t tq = (i >= 1 && cx.bulk && trtri_own_queue && own_events) ? cx.bulk : cx.aux;
             // (all I_i share ONE level scratch: the previous one must be through with it -- an explicit event, not "it
             //  finished long ago": with several handles alive HIP multiplexes their streams onto a few hardware queues and
@@ -828,8 +832,7 @@ static int invk_lower(const Ctx& cx, Workspace& ws, int n, const int* zmap = nul
     p.M = Np; p.N = Np; p.K = Np; p.lower = 1;
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
-    static const int persist_env = getenv("GPMPC_VARGEMM_PERSIST") ? atoi(getenv("GPMPC_VARGEMM_PERSIST")) : 1;
-    const int persist = g_vargemm_persist >= 0 ? g_vargemm_persist : persist_env;
+    const int persist = vargemm_persist_mode();
     const int T = (Np + VAR_TILE - 1) / VAR_TILE, slots = 2 * g_cu_count[dev];
     double total = 0.0;
     for (int tm = 0; tm < T; ++tm) total += (double)(tm + 1) * (2 * ((Np - tm * VAR_TILE) / 16) + 1);

@@ -59,7 +59,7 @@ static int factor_with_jitter(gpmpc_gp* h, Workspace& ws, const double* hyper_ho
         HIPCHK(hipMemcpyAsync(ws.jitter, jit.data(), nb * sizeof(double), hipMemcpyHostToDevice, h->stream));
         // (TailState) with the tile-owner workers the status words come back when the chain kernel ends, on the workers'
         // queue: this call then returns with the tail of the inverse (and `post`) still in flight on the main queue
-        static const bool early_status = !(getenv("GPMPC_EARLY_STATUS") && atoi(getenv("GPMPC_EARLY_STATUS")) == 0);
+        static const bool early_status = env_int("GPMPC_EARLY_STATUS", 1) != 0;
         h->tail.pin_info = pin_info; h->tail.cerr = cerr; h->tail.nflag = nflag; h->tail.nb = nb;
         h->tail.ev_info = h->ev_info;
         h->tail.want_early = early_status && !g_chain_trace;
@@ -72,7 +72,7 @@ static int factor_with_jitter(gpmpc_gp* h, Workspace& ws, const double* hyper_ho
             if (check_chain) HIPCHK(hipMemcpyAsync(cerr, ws.flags, nflag * sizeof(int), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipEventRecord(h->ev_info, h->stream));
         }
-        static const bool post_early = !(getenv("GPMPC_POST_EARLY") && atoi(getenv("GPMPC_POST_EARLY")) == 0);
+        static const bool post_early = env_int("GPMPC_POST_EARLY", 1) != 0;
         if (post && post_early) post();
         HIPCHK(hipEventSynchronize(h->ev_info));
         if (post && !post_early) post();
@@ -172,14 +172,14 @@ static int fit_impl(gpmpc_gp* h, const double* hyper, int want_invK, int* info, 
     alpha_ready(h);                      // (a previous fit's alpha launches on the workers' queue: ordered before this fit's)
     bool alpha_on_side = false;
     CHK(factor_with_jitter(h, h->ws, kpart.data(), info, [&]() {
-        static const bool alpha_side_env = !(getenv("GPMPC_ALPHA_SIDE") && atoi(getenv("GPMPC_ALPHA_SIDE")) == 0);
+        static const bool alpha_side_env = env_int("GPMPC_ALPHA_SIDE", 1) != 0;
         alpha_on_side = h->tail.early_done && alpha_side_env && !want_invK && h->side_stream;
         if (alpha_on_side) {
             // the fit returns at the end of the chain kernel.  w = L^-1 y follows the inverse's tail on the main queue (r06: it
             // used to cross to the workers' queue first, two event hand-overs in front of a variance product that needs it for
             // its fused mean), the rest of alpha goes to the workers' queue, so that what the caller enqueues next on the main
             // queue -- a variance product -- follows w directly.  GPMPC_W_MAIN=0: all of alpha on the workers' queue, as r05.
-            static const bool w_main = !(getenv("GPMPC_W_MAIN") && atoi(getenv("GPMPC_W_MAIN")) == 0);
+            static const bool w_main = env_int("GPMPC_W_MAIN", 1) != 0;
             Ctx cs = h->cx();
             cs.stream = h->side_stream;
             if (w_main) {
@@ -233,15 +233,11 @@ extern "C" int gpmpc_fit(gpmpc_gp* h, const double* hyper, int want_invK, int* i
 //     inv22 = L22^-1;   inv21 = -inv22 (L21 inv11)
 // i.e. four GEMMs with K = R0 plus a factorisation of m rows -- O(N^2 m) instead of O(N^3).
 static void free_predict_scratch(gpmpc_gp* h) {
-    hipFree(h->Z); hipFree(h->Sigma); hipFree(h->KsT); hipFree(h->part); hipFree(h->partm); hipFree(h->meanT);
-    hipFree(h->mean); hipFree(h->var); hipFree(h->J); hipFree(h->cov); hipFree(h->UT); hipFree(h->VT);
-    hipFree(h->sensH); hipFree(h->sensV); hipFree(h->em); hipFree(h->ems); hipFree(h->beta); hipFree(h->gradPartial); hipFree(h->gradOut);
-    hipFree(h->ccpart); hipFree(h->Yc); hipFree(h->tYc);
+    free_chunk_buffers(h);
+    hipFree(h->em); hipFree(h->ems); hipFree(h->beta); hipFree(h->gradPartial); hipFree(h->gradOut);
+    hipFree(h->Yc); hipFree(h->tYc);
     h->Yc = h->tYc = nullptr;
-    h->partm = nullptr;
-    h->Z = h->Sigma = h->KsT = h->part = h->meanT = h->mean = h->var = h->J = h->cov = h->UT = h->VT = nullptr;
-    h->sensH = h->sensV = h->em = h->ems = h->beta = h->gradPartial = h->gradOut = h->ccpart = nullptr;
-    h->Bcap = 0;
+    h->em = h->ems = h->beta = h->gradPartial = h->gradOut = nullptr;
     h->emBytes = h->emsBytes = 0;
     h->have_beta = false;
     ws_free(h->tws);

@@ -231,8 +231,8 @@ static int create_impl(gpmpc_gp* h, const double* X, const double* Y) {
     // 0: single queue; 1: chained Cholesky, bulk in GEMM launches; 2: + inverse pipelined behind the chain;
     // 3: + bulk in the persistent tile-owner kernel where the matrix fits its registers (else as 2)
     h->chain_mode = 3;
-    if (const char* e = getenv("GPMPC_CHAIN")) h->chain_mode = atoi(e);
-    if (const char* e = getenv("GPMPC_SPIN_LIMIT")) h->spin_limit = atoi(e);   // tests: force the hand-off time-out path
+    h->chain_mode = env_int("GPMPC_CHAIN", h->chain_mode);
+    h->spin_limit = env_int("GPMPC_SPIN_LIMIT", h->spin_limit);   // tests: force the hand-off time-out path
     const int Np = h->Np;
     std::vector<double> xt((size_t)d * Np, 0.0), yt((size_t)Ny * Np, 0.0);
     for (int i = 0; i < N; ++i) {
@@ -273,6 +273,16 @@ int gpmpc_create(int device, int N, int d, int Ny, const double* X, const double
     return GPMPC_OK;
 }
 
+// The predict scratch sized by Bcap (ensure_scratch, api_predict.inl, and what gpmpc_predict_sens adds to it): the one list
+static void free_chunk_buffers(gpmpc_gp* h) {
+    for (double** p : {&h->Z, &h->Sigma, &h->KsT, &h->part, &h->partm, &h->meanT, &h->mean, &h->var, &h->J, &h->cov, &h->UT, &h->VT,
+                       &h->sensH, &h->sensV, &h->ccpart}) {
+        hipFree(*p);
+        *p = nullptr;
+    }
+    h->Bcap = 0;
+}
+
 static void drop_roll_graphs(gpmpc_gp* h) {
 #ifndef GPMPC_EMULATED
     for (auto& g : h->roll_graphs) {
@@ -296,9 +306,8 @@ int gpmpc_destroy(gpmpc_gp* h) {
     hipFree(h->bYc); hipFree(h->bmpar); hipFree(h->bgradPartial); hipFree(h->bgradOut); hipFree(h->bzmap);
     hipFree(h->XT); hipFree(h->Y); hipFree(h->gradPartial); hipFree(h->gradOut);
     hipFree(h->mpar); hipFree(h->Yc); hipFree(h->tmpar); hipFree(h->tYc);
-    hipFree(h->Z); hipFree(h->Sigma); hipFree(h->KsT); hipFree(h->part); hipFree(h->partm); hipFree(h->meanT);
-    hipFree(h->mean); hipFree(h->var); hipFree(h->J); hipFree(h->cov); hipFree(h->em); hipFree(h->ems);
-    hipFree(h->beta); hipFree(h->UT); hipFree(h->VT); hipFree(h->sensH); hipFree(h->sensV); hipFree(h->ccpart);
+    free_chunk_buffers(h);
+    hipFree(h->em); hipFree(h->ems); hipFree(h->beta);
     for (int ph = 0; ph < GPMPC_PH_COUNT; ++ph)
         for (auto& pr : h->prof.ev[ph]) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     for (auto e : h->prof.pool) hipEventDestroy(e);

@@ -58,7 +58,7 @@ extern "C" int gpmpc_dgemm(int device, int transa, int transb, int M, int N, int
     p.C = dC; p.ldc = N;
     p.M = M; p.N = N; p.K = Kp; p.alpha = alpha; p.beta = beta;
     // GPMPC_DGEMM_TILE=128|64|32 pins the tile (tests reach the large-tile kernels with small matrices)
-    launch_gemm(p, 1, cx.stream, getenv("GPMPC_DGEMM_TILE") ? atoi(getenv("GPMPC_DGEMM_TILE")) : 0);
+    launch_gemm(p, 1, cx.stream, env_int("GPMPC_DGEMM_TILE", 0));
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(c.data(), dC, c.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -156,7 +156,7 @@ extern "C" int gpmpc_set_tuning(const char* name, int value) {
     }
     if (std::strcmp(name, "fail_nll_after") == 0) {      // fault injection for the tests of the restart shard's failure paths
         if (value < 0) return fail(GPMPC_EINVAL, "fail_nll_after must be >= 0");
-        static const bool testing = getenv("GPMPC_TESTING") && atoi(getenv("GPMPC_TESTING")) != 0;
+        static const bool testing = env_int("GPMPC_TESTING", 0) != 0;
         if (!testing) return fail(GPMPC_EINVAL, "fail_nll_after is a test knob: start the process with GPMPC_TESTING=1");
         g_fail_nll_after.store(value);
         return GPMPC_OK;

@@ -1,5 +1,5 @@
 // api_predict.inl -- part of gpmpc_api.hip (one translation unit; included in order, not compiled alone).
-// Concern: predict: I/O staging, mean / variance / Jacobian chunks, moment methods, derivative outputs, GP.covar.
+// Concern: predict: chunk I/O (ChunkIo), the variance plan (var_plan), mean / variance / Jacobian chunks, moment methods, derivative outputs, GP.covar.
 // ------------------------------------------------------------------------------------------------
 // predict
 // ------------------------------------------------------------------------------------------------
@@ -19,28 +19,43 @@ static int chunk_size(const gpmpc_gp* h) {
 // Points per pass of the chunk loops: the scratch's capacity, or less when "predict_chunk" was lowered on a live handle
 static int chunk_step(const gpmpc_gp* h) { return std::min(h->Bcap, chunk_size(h)); }
 
-// Host-pointer calls with little data (an MPC's shooting nodes at the reference's model sizes): the inputs are staged in
-// a pinned buffer and go up in one copy, every output is a slice of one device block and comes down in one copy.  With a
-// pageable hipMemcpyAsync per array a 'ME' prediction at N = 200 took 71 us of which the kernels are 30
-// (tools/gpu_small_latency.sh); packed it takes one upload, the launches, one download and one synchronisation.
+// Chunk I/O of the predict family: one object for the three pointer modes.  Declare every input with in(), upload(),
+// declare every output with out(), launch, download().
+//   device pointers: the caller's arrays are read and written in place; no copies, no synchronisation.
+//   host pointers, little data (an MPC's shooting nodes at the reference's model sizes): the inputs are staged in a pinned
+//     buffer and go up in one copy, every output is a slice of one device block and comes down in one copy.  With a pageable
+//     hipMemcpyAsync per array a 'ME' prediction at N = 200 took 71 us of which the kernels are 30
+//     (tools/gpu_small_latency.sh); packed it takes one upload, the launches, one download and one synchronisation.
+//   host pointers beyond IO_PACK_DOUBLES: one hipMemcpyAsync per array each way through the handle's staging buffers, in the
+//     order of the declarations, then one synchronisation.
 constexpr size_t IO_PACK_DOUBLES = 32768;      // 256 KB
-struct IoPack {
-    gpmpc_gp* h;
-    bool on = false;
-    size_t nin = 0, n = 0;
-    struct Out { double* host; size_t off, cnt; };
-    std::vector<Out> outs;
+struct ChunkIo {
+    enum Mode { DEVICE, PACKED, UNPACKED };
+    struct Xfer { double *host, *dev; size_t cnt; };
+    gpmpc_gp* h = nullptr;
+    Mode mode = DEVICE;
+    size_t nin = 0, n = 0;                       // packed: doubles of the inputs / of everything declared so far
+    Xfer ins[2], outs[6];
+    int n_ins = 0, n_outs = 0;
     static size_t pad(size_t c) { return (c + 1) & ~(size_t)1; }     // slices stay 16-byte aligned
-    // total: doubles of all inputs and outputs (each padded); false -> the caller copies array by array as before
-    int begin(gpmpc_gp* hh, bool host, size_t total) {
+    // counts: doubles of every input and output that will be declared (0 for one that is left out)
+    int begin(gpmpc_gp* hh, bool host, std::initializer_list<size_t> counts) {
         h = hh;
-        on = host && total <= IO_PACK_DOUBLES;
-        if (!on) return GPMPC_OK;
+        size_t total = 0;
+        for (size_t c : counts) total += pad(c);
+        mode = !host ? DEVICE : total <= IO_PACK_DOUBLES ? PACKED : UNPACKED;
+        if (mode != PACKED) return GPMPC_OK;
         if (!h->io_dev) HIPCHK(hipMalloc(&h->io_dev, IO_PACK_DOUBLES * sizeof(double)));
         if (!h->io_pin) HIPCHK(hipHostMalloc((void**)&h->io_pin, IO_PACK_DOUBLES * sizeof(double), hipHostMallocDefault));
         return GPMPC_OK;
     }
-    const double* in(const double* src, size_t cnt) {                  // call for all inputs first, then upload()
+    bool packed() const { return mode == PACKED; }
+    const double* in(const double* src, size_t cnt, double* staging) {  // the device pointer to read
+        if (mode == DEVICE) return src;
+        if (mode == UNPACKED) {
+            ins[n_ins++] = {const_cast<double*>(src), staging, cnt};
+            return staging;
+        }
         std::memcpy(h->io_pin + n, src, cnt * sizeof(double));
         const double* dptr = h->io_dev + n;
         n += pad(cnt);
@@ -49,19 +64,30 @@ struct IoPack {
     }
     int upload() {
         if (nin) HIPCHK(hipMemcpyAsync(h->io_dev, h->io_pin, nin * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        for (int i = 0; i < n_ins; ++i)
+            HIPCHK(hipMemcpyAsync(ins[i].dev, ins[i].host, ins[i].cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
         return GPMPC_OK;
     }
-    double* out(double* host_dst, size_t cnt) {                        // device slice for an output (nullptr for a NULL output)
-        if (!host_dst) return nullptr;
-        outs.push_back({host_dst, n, cnt});
-        double* dptr = h->io_dev + n;
-        n += pad(cnt);
+    // the device pointer to write; a NULL output: nullptr, or `staging` where the launches need the array all the same
+    double* out(double* user, size_t cnt, double* staging, bool keep_if_null = false) {
+        if (!user) return keep_if_null ? staging : nullptr;
+        if (mode == DEVICE) return user;
+        double* dptr = mode == PACKED ? h->io_dev + n : staging;
+        if (mode == PACKED) n += pad(cnt);
+        outs[n_outs++] = {user, dptr, cnt};
         return dptr;
     }
-    int download() {                                                   // one copy, one synchronisation, scatter on the host
-        if (n > nin) HIPCHK(hipMemcpyAsync(h->io_pin + nin, h->io_dev + nin, (n - nin) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    int download() {
+        if (mode == DEVICE) return GPMPC_OK;
+        if (mode == PACKED) {                                          // one copy, one synchronisation, scatter on the host
+            if (n > nin) HIPCHK(hipMemcpyAsync(h->io_pin + nin, h->io_dev + nin, (n - nin) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            for (int i = 0; i < n_outs; ++i) std::memcpy(outs[i].host, h->io_pin + (outs[i].dev - h->io_dev), outs[i].cnt * sizeof(double));
+            return GPMPC_OK;
+        }
+        for (int i = 0; i < n_outs; ++i)
+            HIPCHK(hipMemcpyAsync(outs[i].host, outs[i].dev, outs[i].cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        for (const Out& o : outs) std::memcpy(o.host, h->io_pin + o.off, o.cnt * sizeof(double));
         return GPMPC_OK;
     }
 };
@@ -73,12 +99,7 @@ static int ensure_scratch(gpmpc_gp* h, int B, bool keep_tail = false) {
     const int need = round_up(B < chunk_size(h) ? B : chunk_size(h), 64);
     if (need <= h->Bcap) return GPMPC_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
-    hipFree(h->Z); hipFree(h->Sigma); hipFree(h->KsT); hipFree(h->part); hipFree(h->partm); hipFree(h->meanT);
-    hipFree(h->mean); hipFree(h->var); hipFree(h->J); hipFree(h->cov); hipFree(h->UT); hipFree(h->VT);
-    hipFree(h->sensH); hipFree(h->sensV); hipFree(h->ccpart);
-    h->UT = h->VT = h->sensH = h->sensV = h->ccpart = h->partm = nullptr;
-    h->Z = h->Sigma = h->KsT = h->part = h->meanT = h->mean = h->var = h->J = h->cov = nullptr;
-    h->Bcap = 0;
+    free_chunk_buffers(h);
     const size_t d = h->d, Ny = h->Ny, Np = h->Np, Bc = need;
     HIPCHK(hipMalloc(&h->Z, Bc * d * sizeof(double)));
     HIPCHK(hipMalloc(&h->Sigma, Bc * d * d * sizeof(double)));
@@ -96,6 +117,95 @@ static int ensure_scratch(gpmpc_gp* h, int B, bool keep_tail = false) {
     return GPMPC_OK;
 }
 
+// The variance product V = L^-1 Ks of one chunk, reduced to column sums of squares: which kernel forms it and with what.
+// Decided once per chunk, before the cross-covariances are formed, because the persistent kernel also offers the mean.
+enum VarRoute {
+    VAR_NONE,         // no variance wanted
+    VAR_ONE_ROW,      // B <= GPMPC_VARSMALL_MAX: a dedicated kernel streams L^-1 once, one row (or a few) per wave
+    VAR_SKINNY_DMA,   // B <= 64: a row tile x all columns per workgroup, DMA-staged
+    VAR_SKINNY_REG,   //          the same, register-staged (GPMPC_SMALLB_DMA=0 or operands the DMA kernel cannot take)
+    VAR_PERSIST,      // 128-row tiles, one persistent launch over a static schedule (vargemm_persist.hpp)
+    VAR_TILES         // the dispatcher's tiles (launch_gemm)
+};
+struct VarPlan {
+    VarRoute route = VAR_NONE;
+    GemmP p;                                    // every route but VAR_NONE / VAR_ONE_ROW
+    int tile = 0, tilesM = 0, tilesN = 0;       // tile edge (VAR_PERSIST / VAR_TILES), row tiles = rows of `part` per point, column tiles
+    int rpw = 0, slots = 0;                     // VAR_ONE_ROW: rows per wave; VAR_PERSIST: workgroup slots of the schedule
+    bool fused_mean_ok() const { return route == VAR_PERSIST; }   // its reduction sum_i V_ij w_i, w = L^-1 y, is there to be had
+};
+
+// VT (optional): the product itself is kept as well, V^T = (L^-1 Ks)^T, [Ny][Bp][Np] (the sensitivities)
+static VarPlan var_plan(const gpmpc_gp* h, const Ctx& cx, int B, double* VT) {
+    VarPlan v;
+    const int Bp = round_up(B, 32), Np = h->Np, Ny = h->Ny;
+    // One point: a dedicated kernel streams L^-1 once at 5.6 TB/s (C3 size).  Measured at N = 8192, Ny = 6
+    // (tools/bench_smallb.py), its multi-column versions fall off quickly (B = 2 / 4 / 8: 0.41 / 0.52 / 0.82 ms)
+    // while the DMA-staged GEMM below does any B <= 32 in 0.30-0.32 ms: GPMPC_VARSMALL_MAX (default 1) is the switch.
+    static const int varsmall_max = env_int("GPMPC_VARSMALL_MAX", 1);
+    if (!VT && B <= varsmall_max && B <= 8) {
+        static const int rpw_env = env_int("GPMPC_VARSMALL_RPW", 0);   // (tuning aid: rows per wave, 1 .. 8)
+        v.route = VAR_ONE_ROW;
+        v.rpw = (rpw_env >= 1 && rpw_env <= 8 && Np % (4 * rpw_env) == 0) ? rpw_env : var_small_rows_per_wave(Np, Ny, g_cu_count[h->device]);
+        v.tilesM = Np / (4 * v.rpw);
+        return v;
+    }
+    GemmP& p = v.p;
+    p = gemm_base(cx);
+    p.A = h->ws.Inv; p.lda = Np; p.sA = (long)Np * Np; p.a_mc = 0; p.kflags = KA_LE_M;
+    p.B = h->KsT; p.ldb = Np; p.sB = (long)Bp * Np; p.b_nc = 0;
+    p.M = Np; p.N = Bp; p.K = Np;
+    p.epi = EPI_COLSUMSQ; p.part = h->part; p.ldpart = Bp;
+    p.Ct = VT; p.ldct = Np; p.sCt = (long)Bp * Np;
+    if (B <= 64) {
+        // small batch (an MPC's Nt shooting nodes): tall-skinny tiles, a row tile x all columns per workgroup,
+        // so that L^-1 is streamed once and the small Ks panel is shared through LDS.  The stream is what matters:
+        // the DMA-staged kernel with a THREE-image ring and 64-row tiles (several workgroups per CU, each with two
+        // slabs in flight) reaches 5.0 TB/s of L^-1 at N = 8192, Ny = 6, B <= 32 (0.32 ms; four / five images 0.33 /
+        // 0.34, 32-row tiles 0.39, 128-row tiles 0.40) where the register-staged 32-row kernel managed 3.5 TB/s
+        // (0.46 ms; 128 rows 0.52, 64 rows 0.53, 16 rows 0.56).  33-64 columns: 64 x 64 tiles, 0.54 against 0.70 ms.
+        // (A no-LDS direct-fragment streaming kernel, which re-reads the Ks panel from L2 once per row tile, was
+        //  slower still: 0.66 ms at B = 30.)  GPMPC_SMALLB_DMA=0 selects the register-staged kernels.
+        static const bool smallb_dma = env_int("GPMPC_SMALLB_DMA", 1) != 0;
+        v.route = smallb_dma && gemm_dma_supported(p) ? VAR_SKINNY_DMA : VAR_SKINNY_REG;
+        const int tm_rows = v.route == VAR_SKINNY_DMA ? 64 : Bp <= 32 ? 32 : 128;
+        v.tilesM = (Np + tm_rows - 1) / tm_rows;
+    } else {
+        v.tile = g_gemm_force_tile ? g_gemm_force_tile : gemm_pick_tile(p, Ny);
+        v.tilesM = (Np + v.tile - 1) / v.tile;
+        v.tilesN = (Bp + VAR_TILE - 1) / VAR_TILE;
+        v.slots = 2 * g_cu_count[h->device];
+        // 128-row tiles and at least two of them per workgroup slot: one persistent launch over a static schedule
+        // (vargemm_persist.hpp; GPMPC_VARGEMM_PERSIST=0 / tuning knob 'vargemm_persist' 0: the dispatcher's order)
+        const int persist = vargemm_persist_mode();
+        const bool persistent = persist && v.tile == VAR_TILE && !VT && Ny < 256 && v.tilesM < 4096 && v.tilesN < 4096 &&
+                                gemm_dma_supported(p) && (long)v.tilesM * v.tilesN * Ny >= (persist > 1 ? 1 : 2L * v.slots);
+        v.route = persistent ? VAR_PERSIST : VAR_TILES;
+    }
+    p.sPart = (long)v.tilesM * Bp;
+    return v;
+}
+
+// VT[j][i] (+)= sum_k KsT[j][k] invL[i][k]: V^T = Ks^T L^-T of Bp points, [Ny][Bp][Np]; beta = 1 adds to what VT holds
+static void launch_vt(const Ctx& cx, const double* KsT, const double* Inv, double* VT, int Bp, int Np, int Ny, double beta = 0.0) {
+    GemmP p = gemm_base(cx);
+    p.A = KsT; p.lda = Np; p.sA = (long)Bp * Np; p.a_mc = 0;
+    p.B = Inv; p.ldb = Np; p.sB = (long)Np * Np; p.b_nc = 0; p.kflags = KB_LE_N;
+    p.C = VT; p.ldc = Np; p.sC = (long)Bp * Np;
+    p.M = Bp; p.N = Np; p.K = Np; p.beta = beta;
+    launch_gemm(p, Ny, cx.stream);
+}
+
+// C = -VT VT^T, [Ny][Bp][Bp]
+static void launch_neg_gram(const Ctx& cx, const double* VT, double* C, int Bp, int Np, int Ny) {
+    GemmP q = gemm_base(cx);
+    q.A = VT; q.lda = Np; q.sA = (long)Bp * Np; q.a_mc = 0;
+    q.B = VT; q.ldb = Np; q.sB = (long)Bp * Np; q.b_nc = 0;
+    q.C = C; q.ldc = Bp; q.sC = (long)Bp * Bp;
+    q.M = Bp; q.N = Bp; q.K = Np; q.alpha = -1.0;
+    launch_gemm(q, Ny, cx.stream);
+}
+
 // One chunk (B <= Bcap) with device pointers: mean/var (either may be NULL), optional J.
 // VT (optional, with dVar): also keep V^T = (L^-1 Ks)^T, [Ny][Bp][Np], for the sensitivities
 // behind_tail: this is the first use of the predict scratch behind a gpmpc_fit that returned at the end of its chain
@@ -110,33 +220,21 @@ static int predict_chunk(gpmpc_gp* h, int B, const double* dZ, double* dMean, do
                          bool behind_tail = false) {
     const Ctx cx = h->cx();
     const int Bp = round_up(B, 32), Np = h->Np, Ny = h->Ny;
-    int tilesM = 0;
-    static const int overlap_env = getenv("GPMPC_PREDICT_OVERLAP") ? atoi(getenv("GPMPC_PREDICT_OVERLAP")) : 1;
+    static const int overlap_env = env_int("GPMPC_PREDICT_OVERLAP", 1);
     const bool overlapped = behind_tail && overlap_env && dVar && !dJ && !VT && B > 64 && cx.bulk && cx.side &&
                             h->stream == h->own_stream;
     TailState& ts = h->tail;
     // Large batches whose variance product runs as the persistent kernel take the mean from its fused reduction
     // (sum_i V_ij w_i, w = L^-1 y: vargemm_persist.hpp) instead of from the cross-covariance kernel or a kernel of its own:
-    // decided here, before the cross-covariances are formed (GPMPC_FUSED_MEAN=0: as before).
-    static const int persist_env0 = getenv("GPMPC_VARGEMM_PERSIST") ? atoi(getenv("GPMPC_VARGEMM_PERSIST")) : 1;
-    static const bool fused_mean_env = !(getenv("GPMPC_FUSED_MEAN") && atoi(getenv("GPMPC_FUSED_MEAN")) == 0);
-    bool fused_mean = false;
-    if (dVar && dMean && !dJ && !VT && B > 64 && fused_mean_env) {
-        const int persist0 = g_vargemm_persist >= 0 ? g_vargemm_persist : persist_env0;
-        const int tM = (Np + VAR_TILE - 1) / VAR_TILE, tN = (Bp + VAR_TILE - 1) / VAR_TILE, slots0 = 2 * g_cu_count[h->device];
-        GemmP q = gemm_base(cx);
-        q.A = h->ws.Inv; q.lda = Np; q.sA = (long)Np * Np; q.kflags = KA_LE_M;
-        q.B = h->KsT; q.ldb = Np; q.sB = (long)Bp * Np;
-        q.M = Np; q.N = Bp; q.K = Np;
-        const int tile0 = g_gemm_force_tile ? g_gemm_force_tile : gemm_pick_tile(q, Ny);
-        fused_mean = persist0 && tile0 == VAR_TILE && Ny < 256 && tM < 4096 && tN < 4096 && gemm_dma_supported(q) &&
-                     (long)tM * tN * Ny >= (persist0 > 1 ? 1 : 2L * slots0);
-    }
+    // known here, before the cross-covariances are formed (GPMPC_FUSED_MEAN=0: as before).
+    const VarPlan vp = dVar ? var_plan(h, cx, B, VT) : VarPlan();
+    static const bool fused_mean_env = env_int("GPMPC_FUSED_MEAN", 1) != 0;
+    const bool fused_mean = vp.fused_mean_ok() && dMean && !dJ && fused_mean_env;
     if (overlapped) {
         // (GPMPC_CROSSCOV_WGS: workgroups of the throttled launch; 0 = one per block of test points, i.e. not throttled)
         // (r05: half a workgroup per CU -- the launch is longer, 0.31 against 0.22 ms, still ends with the tail, and takes less
         //  from the tail's latency-bound launches: step -11 ... -25 us on two boxes, profiles/r05_sweep_cuts_throttle.txt)
-        static const int cc_wgs = getenv("GPMPC_CROSSCOV_WGS") ? atoi(getenv("GPMPC_CROSSCOV_WGS")) : std::max(1, g_cu_count[h->device] / 2);
+        static const int cc_wgs = env_int("GPMPC_CROSSCOV_WGS", std::max(1, g_cu_count[h->device] / 2));
         {
             // (gpmpc_fit_predict_mean_var enqueues this before the chain has ended: the launch waits for the chain's end)
             if (ts.fused_early && ts.ev_chain) hipStreamWaitEvent(cx.bulk, ts.ev_chain, 0);
@@ -168,71 +266,29 @@ static int predict_chunk(gpmpc_gp* h, int B, const double* dZ, double* dMean, do
         launch_crosscov(cx.stream, h->d, h->XT, h->ws.hyper, fused_mean ? nullptr : h->ws.alpha, dZ, h->KsT, h->meanT, dJ, h->N, Np, B, Bp, Ny,
                         h->ccpart, nch);
     }
-    // One point: a dedicated kernel streams L^-1 once at 5.6 TB/s (C3 size).  Measured at N = 8192, Ny = 6
-    // (tools/bench_smallb.py), its multi-column versions fall off quickly (B = 2 / 4 / 8: 0.41 / 0.52 / 0.82 ms)
-    // while the DMA-staged GEMM below does any B <= 32 in 0.30-0.32 ms: GPMPC_VARSMALL_MAX (default 1) is the switch.
-    static const int varsmall_max = getenv("GPMPC_VARSMALL_MAX") ? atoi(getenv("GPMPC_VARSMALL_MAX")) : 1;
-    if (dVar && !VT && B <= varsmall_max && B <= 8) {
-        PhaseTimer t(h, GPMPC_PH_VARGEMM);   // stream L^-1 once (HBM-bound), no MFMA padding waste
-        static const int rpw_env = getenv("GPMPC_VARSMALL_RPW") ? atoi(getenv("GPMPC_VARSMALL_RPW")) : 0;   // (tuning aid: rows per wave, 1 .. 8)
-        const int rpw = (rpw_env >= 1 && rpw_env <= 8 && Np % (4 * rpw_env) == 0) ? rpw_env : var_small_rows_per_wave(Np, Ny, g_cu_count[h->device]);
-        tilesM = Np / (4 * rpw);
-        const dim3 grid(tilesM, Ny);
-        if (B == 1) hipLaunchKernelGGL((var_small_kernel<1>), grid, dim3(256), 0, cx.stream, h->ws.Inv, h->KsT, h->part, Np, Bp, rpw);
-        else if (B == 2) hipLaunchKernelGGL((var_small_kernel<2>), grid, dim3(256), 0, cx.stream, h->ws.Inv, h->KsT, h->part, Np, Bp, rpw);
-        else if (B <= 4) hipLaunchKernelGGL((var_small_kernel<4>), grid, dim3(256), 0, cx.stream, h->ws.Inv, h->KsT, h->part, Np, Bp, rpw);
-        else hipLaunchKernelGGL((var_small_kernel<8>), grid, dim3(256), 0, cx.stream, h->ws.Inv, h->KsT, h->part, Np, Bp, rpw);
-    } else if (dVar && B <= 64) {
-        // small batch (an MPC's Nt shooting nodes): tall-skinny tiles, a row tile x all columns per workgroup,
-        // so that L^-1 is streamed once and the small Ks panel is shared through LDS.  The stream is what matters:
-        // the DMA-staged kernel with a THREE-image ring and 64-row tiles (several workgroups per CU, each with two
-        // slabs in flight) reaches 5.0 TB/s of L^-1 at N = 8192, Ny = 6, B <= 32 (0.32 ms; four / five images 0.33 /
-        // 0.34, 32-row tiles 0.39, 128-row tiles 0.40) where the register-staged 32-row kernel managed 3.5 TB/s
-        // (0.46 ms; 128 rows 0.52, 64 rows 0.53, 16 rows 0.56).  33-64 columns: 64 x 64 tiles, 0.54 against 0.70 ms.
-        // (A no-LDS direct-fragment streaming kernel, which re-reads the Ks panel from L2 once per row tile, was
-        //  slower still: 0.66 ms at B = 30.)  GPMPC_SMALLB_DMA=0 selects the register-staged kernels.
+    if (vp.route != VAR_NONE) {
         PhaseTimer t(h, GPMPC_PH_VARGEMM);
-        GemmP p = gemm_base(cx);
-        p.A = h->ws.Inv; p.lda = Np; p.sA = (long)Np * Np; p.a_mc = 0; p.kflags = KA_LE_M;
-        p.B = h->KsT; p.ldb = Np; p.sB = (long)Bp * Np; p.b_nc = 0;
-        p.M = Np; p.N = Bp; p.K = Np;
-        p.epi = EPI_COLSUMSQ; p.part = h->part; p.ldpart = Bp;
-        p.Ct = VT; p.ldct = Np; p.sCt = (long)Bp * Np;
-        static const bool smallb_dma = !(getenv("GPMPC_SMALLB_DMA") && atoi(getenv("GPMPC_SMALLB_DMA")) == 0);
-        const bool dma = smallb_dma && gemm_dma_supported(p);
-        const int tm_rows = dma ? 64 : Bp <= 32 ? 32 : 128;
-        tilesM = (Np + tm_rows - 1) / tm_rows;
-        p.sPart = (long)tilesM * Bp;
-        if (dma && Bp <= 32) launch_gemm_dma<64, 32, 4, 1, 3, 4>(p, Ny, cx.stream, 1 << 30, 2);
-        else if (dma) launch_gemm_dma<64, 64, 2, 2, 3, 4>(p, Ny, cx.stream, 1 << 30, 2);
-        else if (Bp <= 32) launch_gemm_cfg<32, 32, 32, 2, 1>(p, Ny, cx.stream, 1 << 30, 2);
-        else launch_gemm_cfg<128, 64, 16, 4, 2>(p, Ny, cx.stream, 1 << 30, 2);
-    } else if (dVar) {
-        PhaseTimer t(h, GPMPC_PH_VARGEMM);
-        GemmP p = gemm_base(cx);  // V = L^-1 Ks, reduced to column sums of squares in the epilogue
-        p.A = h->ws.Inv; p.lda = Np; p.sA = (long)Np * Np; p.a_mc = 0; p.kflags = KA_LE_M;
-        p.B = h->KsT; p.ldb = Np; p.sB = (long)Bp * Np; p.b_nc = 0;
-        p.M = Np; p.N = Bp; p.K = Np;
-        p.epi = EPI_COLSUMSQ; p.part = h->part; p.ldpart = Bp;
-        p.Ct = VT; p.ldct = Np; p.sCt = (long)Bp * Np;
-        const int tile = g_gemm_force_tile ? g_gemm_force_tile : gemm_pick_tile(p, Ny);
-        tilesM = (Np + tile - 1) / tile;
-        p.sPart = (long)tilesM * Bp;
-        // 128-row tiles and at least two of them per workgroup slot: one persistent launch over a static schedule
-        // (vargemm_persist.hpp; GPMPC_VARGEMM_PERSIST=0 / tuning knob 'vargemm_persist' 0: the dispatcher's order)
-        static const int persist_env = getenv("GPMPC_VARGEMM_PERSIST") ? atoi(getenv("GPMPC_VARGEMM_PERSIST")) : 1;
-        const int persist = g_vargemm_persist >= 0 ? g_vargemm_persist : persist_env;
-        const int slots = 2 * g_cu_count[h->device], tilesN = (Bp + VAR_TILE - 1) / VAR_TILE;
-        if (persist && tile == VAR_TILE && !VT && Ny < 256 && tilesM < 4096 && tilesN < 4096 && gemm_dma_supported(p) &&
-            (long)tilesM * tilesN * Ny >= (persist > 1 ? 1 : 2L * slots)) {
+        if (vp.route == VAR_ONE_ROW) {       // stream L^-1 once (HBM-bound), no MFMA padding waste
+            const dim3 grid(vp.tilesM, Ny);
+            if (B == 1) hipLaunchKernelGGL((var_small_kernel<1>), grid, dim3(256), 0, cx.stream, h->ws.Inv, h->KsT, h->part, Np, Bp, vp.rpw);
+            else if (B == 2) hipLaunchKernelGGL((var_small_kernel<2>), grid, dim3(256), 0, cx.stream, h->ws.Inv, h->KsT, h->part, Np, Bp, vp.rpw);
+            else if (B <= 4) hipLaunchKernelGGL((var_small_kernel<4>), grid, dim3(256), 0, cx.stream, h->ws.Inv, h->KsT, h->part, Np, Bp, vp.rpw);
+            else hipLaunchKernelGGL((var_small_kernel<8>), grid, dim3(256), 0, cx.stream, h->ws.Inv, h->KsT, h->part, Np, Bp, vp.rpw);
+        } else if (vp.route == VAR_SKINNY_DMA) {
+            if (Bp <= 32) launch_gemm_dma<64, 32, 4, 1, 3, 4>(vp.p, Ny, cx.stream, 1 << 30, 2);
+            else launch_gemm_dma<64, 64, 2, 2, 3, 4>(vp.p, Ny, cx.stream, 1 << 30, 2);
+        } else if (vp.route == VAR_SKINNY_REG) {
+            if (Bp <= 32) launch_gemm_cfg<32, 32, 32, 2, 1>(vp.p, Ny, cx.stream, 1 << 30, 2);
+            else launch_gemm_cfg<128, 64, 16, 4, 2>(vp.p, Ny, cx.stream, 1 << 30, 2);
+        } else if (vp.route == VAR_PERSIST) {
             VarSchedDev sd;
-            CHK(get_schedule(h->device, PG_VAR, tilesM, tilesN, Ny, Np, slots, &sd));
+            CHK(get_schedule(h->device, PG_VAR, vp.tilesM, vp.tilesN, Ny, Np, vp.slots, &sd));
+            GemmP p = vp.p;
             if (fused_mean) { p.wvec = h->ws.w; p.sWv = Np; p.partm = h->partm; }
             launch_persist_gemm<PG_VAR>(p, sd, cx.stream);
             ++h->n_var_persist;
         } else {
-            if (fused_mean) return fail(GPMPC_EINVAL, "internal: fused mean without the persistent variance product");
-            launch_gemm(p, Ny, cx.stream, tile);
+            launch_gemm(vp.p, Ny, cx.stream, vp.tile);
         }
     }
     if (overlapped && dMean && !fused_mean) {
@@ -242,7 +298,7 @@ static int predict_chunk(gpmpc_gp* h, int B, const double* dZ, double* dMean, do
     {
         PhaseTimer t(h, GPMPC_PH_FINISH);
         hipLaunchKernelGGL(var_finish_kernel, dim3(B), dim3(256), 0, cx.stream, h->part, h->meanT,
-                           h->ws.hyper, dMean, dVar, B, Bp, Ny, h->d, tilesM, fused_mean ? (const double*)h->partm : nullptr);
+                           h->ws.hyper, dMean, dVar, B, Bp, Ny, h->d, vp.tilesM, fused_mean ? (const double*)h->partm : nullptr);
         if (h->mean_kind && h->mean_add && (dMean || dJ))   // build_gp(meanFunc=...): mean += m(z), gp_functions.py:131,135
             hipLaunchKernelGGL(mean_add_kernel, dim3((unsigned)(((long)B * Ny + 255) / 256)), dim3(256), 0, cx.stream, dZ, h->mpar,
                                dMean, dJ, (double*)nullptr, h->mean_kind, B, Ny, h->d);
@@ -283,32 +339,15 @@ static int predict_driver(gpmpc_gp* h, int method, int B, const double* Z, const
         const double* dS = Sigma ? Sigma + (size_t)b0 * d * d : nullptr;
         const bool up_sigma = dS && cov && need_sigma;
         const size_t cZ = (size_t)nb * d, cS = (size_t)nb * d * d, cM = (size_t)nb * Ny, cJ = cM * d, cC = cM * Ny;
-        IoPack io;
-        CHK(io.begin(h, host, IoPack::pad(cZ) + (up_sigma ? IoPack::pad(cS) : 0) + (mean ? IoPack::pad(cM) : 0) +
-                                  (var ? IoPack::pad(cM) : 0) + (J ? IoPack::pad(cJ) : 0) + (cov ? IoPack::pad(cC) : 0)));
-        double *oMean, *oVar, *oJ, *oCov;
-        if (io.on) {
-            dZ = io.in(dZ, cZ);
-            if (up_sigma) dS = io.in(dS, cS);
-            CHK(io.upload());
-            oMean = io.out(mean ? mean + (size_t)b0 * Ny : nullptr, cM);
-            oVar = io.out(var ? var + (size_t)b0 * Ny : nullptr, cM);
-            oJ = io.out(J ? J + (size_t)b0 * Ny * d : nullptr, cJ);
-            oCov = io.out(cov ? cov + (size_t)b0 * Ny * Ny : nullptr, cC);
-        } else {
-            if (host) {
-                HIPCHK(hipMemcpyAsync(h->Z, dZ, cZ * sizeof(double), hipMemcpyHostToDevice, h->stream));
-                dZ = h->Z;
-                if (up_sigma) {
-                    HIPCHK(hipMemcpyAsync(h->Sigma, dS, cS * sizeof(double), hipMemcpyHostToDevice, h->stream));
-                    dS = h->Sigma;
-                }
-            }
-            oMean = mean ? (host ? h->mean : mean + (size_t)b0 * Ny) : nullptr;
-            oVar = var ? (host ? h->var : var + (size_t)b0 * Ny) : nullptr;
-            oJ = J ? (host ? h->J : J + (size_t)b0 * Ny * d) : nullptr;
-            oCov = cov ? (host ? h->cov : cov + (size_t)b0 * Ny * Ny) : nullptr;
-        }
+        ChunkIo io;
+        CHK(io.begin(h, host, {cZ, up_sigma ? cS : 0, mean ? cM : 0, var ? cM : 0, J ? cJ : 0, cov ? cC : 0}));
+        dZ = io.in(dZ, cZ, h->Z);
+        if (up_sigma) dS = io.in(dS, cS, h->Sigma);
+        CHK(io.upload());
+        double* oMean = io.out(mean ? mean + (size_t)b0 * Ny : nullptr, cM, h->mean);
+        double* oVar = io.out(var ? var + (size_t)b0 * Ny : nullptr, cM, h->var);
+        double* oJ = io.out(J ? J + (size_t)b0 * Ny * d : nullptr, cJ, h->J);
+        double* oCov = io.out(cov ? cov + (size_t)b0 * Ny * Ny : nullptr, cC, h->cov);
         if (moments) {
             CHK(predict_moments_chunk(h, method, nb, dZ, dS, oMean ? oMean : h->mean, oCov));
         } else {
@@ -323,15 +362,7 @@ static int predict_driver(gpmpc_gp* h, int method, int B, const double* Z, const
                                    vbuf, jbuf, ta ? dS : (const double*)nullptr, oCov, nb, Ny, d);
             }
         }
-        if (io.on) {
-            CHK(io.download());
-        } else if (host) {
-            if (mean) HIPCHK(hipMemcpyAsync(mean + (size_t)b0 * Ny, h->mean, (size_t)nb * Ny * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            if (var) HIPCHK(hipMemcpyAsync(var + (size_t)b0 * Ny, h->var, (size_t)nb * Ny * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            if (J) HIPCHK(hipMemcpyAsync(J + (size_t)b0 * Ny * d, h->J, (size_t)nb * Ny * d * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            if (cov) HIPCHK(hipMemcpyAsync(cov + (size_t)b0 * Ny * Ny, h->cov, (size_t)nb * Ny * Ny * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-        }
+        CHK(io.download());
     }
     HIPCHK(hipGetLastError());
     return GPMPC_OK;
@@ -357,7 +388,7 @@ extern "C" int gpmpc_fit_predict_mean_var(gpmpc_gp* h, const double* hyper, int 
     CHK(refuse_sparse(h, "gpmpc_fit_predict_mean_var"));
     if (B <= 0 || !Z) return fail(GPMPC_EINVAL, "bad B or NULL Z");
     if (!mean && !var) return fail(GPMPC_EINVAL, "both outputs NULL");
-    static const bool fused_env = !(getenv("GPMPC_FUSED_FIT_PREDICT") && atoi(getenv("GPMPC_FUSED_FIT_PREDICT")) == 0);
+    static const bool fused_env = env_int("GPMPC_FUSED_FIT_PREDICT", 1) != 0;
     const bool fast = fused_env && h->ptr_mode == GPMPC_PTR_DEVICE && !want_invK && var && B > 64 && B <= chunk_size(h) &&
                       h->stream == h->own_stream && h->side_stream && h->bulk_stream && !h->mean_kind;
     if (!fast) {
@@ -413,33 +444,17 @@ extern "C" int gpmpc_predict_sens(gpmpc_gp* h, int B, const double* Z, double* m
     const int step = chunk_step(h);
     for (int b0 = 0; b0 < B; b0 += step) {
         const int nb = (B - b0 < step) ? B - b0 : step;
-        const double* dZ = Z + (size_t)b0 * d;
         const size_t cZ = (size_t)nb * d, cM = (size_t)nb * Ny, cJ = cM * d, cH = cJ * d;
-        IoPack io;
-        CHK(io.begin(h, host, IoPack::pad(cZ) + (mean ? IoPack::pad(cM) : 0) + (var ? IoPack::pad(cM) : 0) + (J ? IoPack::pad(cJ) : 0) +
-                                  (Hm ? IoPack::pad(cH) : 0) + (dvar ? IoPack::pad(cJ) : 0)));
-        double *oMean, *oVar, *oJ, *oH, *oV;
-        if (io.on) {
-            dZ = io.in(dZ, cZ);
-            CHK(io.upload());
-            oMean = io.out(mean ? mean + (size_t)b0 * Ny : nullptr, cM);
-            oVar = io.out(var ? var + (size_t)b0 * Ny : nullptr, cM);
-            oJ = io.out(J ? J + (size_t)b0 * Ny * d : nullptr, cJ);
-            oH = io.out(Hm ? Hm + (size_t)b0 * Ny * d * d : nullptr, cH);
-            oV = io.out(dvar ? dvar + (size_t)b0 * Ny * d : nullptr, cJ);
-            if (!oH) oH = h->sensH;
-            if (!oV) oV = h->sensV;
-        } else {
-            if (host) {
-                HIPCHK(hipMemcpyAsync(h->Z, dZ, cZ * sizeof(double), hipMemcpyHostToDevice, h->stream));
-                dZ = h->Z;
-            }
-            oMean = mean ? (host ? h->mean : mean + (size_t)b0 * Ny) : nullptr;
-            oVar = var ? (host ? h->var : var + (size_t)b0 * Ny) : nullptr;
-            oJ = J ? (host ? h->J : J + (size_t)b0 * Ny * d) : nullptr;
-            oH = host ? h->sensH : (Hm ? Hm + (size_t)b0 * Ny * d * d : h->sensH);
-            oV = host ? h->sensV : (dvar ? dvar + (size_t)b0 * Ny * d : h->sensV);
-        }
+        ChunkIo io;
+        CHK(io.begin(h, host, {cZ, mean ? cM : 0, var ? cM : 0, J ? cJ : 0, Hm ? cH : 0, dvar ? cJ : 0}));
+        const double* dZ = io.in(Z + (size_t)b0 * d, cZ, h->Z);
+        CHK(io.upload());
+        double* oMean = io.out(mean ? mean + (size_t)b0 * Ny : nullptr, cM, h->mean);
+        double* oVar = io.out(var ? var + (size_t)b0 * Ny : nullptr, cM, h->var);
+        double* oJ = io.out(J ? J + (size_t)b0 * Ny * d : nullptr, cJ, h->J);
+        // (the sensitivity kernel writes both of its outputs: the one that is not asked for lands in the handle's staging)
+        double* oH = io.out(Hm ? Hm + (size_t)b0 * Ny * d * d : nullptr, cH, h->sensH, true);
+        double* oV = io.out(dvar ? dvar + (size_t)b0 * Ny * d : nullptr, cJ, h->sensV, true);
         CHK(predict_chunk(h, nb, dZ, oMean, second ? (oVar ? oVar : h->var) : oVar, oJ, second ? h->VT : nullptr));
         if (second) {
             const int Bp = round_up(nb, 32);            // the layout predict_chunk left in KsT and VT
@@ -471,16 +486,7 @@ extern "C" int gpmpc_predict_sens(gpmpc_gp* h, int B, const double* Z, double* m
                 hipLaunchKernelGGL(mean_add_kernel, dim3((unsigned)(((long)nb * Ny + 255) / 256)), dim3(256), 0, cx.stream, dZ,
                                    h->mpar, (double*)nullptr, (double*)nullptr, oH, h->mean_kind, nb, Ny, d);
         }
-        if (io.on) {
-            CHK(io.download());
-        } else if (host) {
-            if (mean) HIPCHK(hipMemcpyAsync(mean + (size_t)b0 * Ny, h->mean, (size_t)nb * Ny * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            if (var) HIPCHK(hipMemcpyAsync(var + (size_t)b0 * Ny, h->var, (size_t)nb * Ny * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            if (J) HIPCHK(hipMemcpyAsync(J + (size_t)b0 * Ny * d, h->J, (size_t)nb * Ny * d * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            if (Hm) HIPCHK(hipMemcpyAsync(Hm + (size_t)b0 * Ny * d * d, h->sensH, (size_t)nb * Ny * d * d * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            if (dvar) HIPCHK(hipMemcpyAsync(dvar + (size_t)b0 * Ny * d, h->sensV, (size_t)nb * Ny * d * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-        }
+        CHK(io.download());
     }
     HIPCHK(hipGetLastError());
     return GPMPC_OK;
@@ -523,9 +529,9 @@ extern "C" int gpmpc_predict_em_sens(gpmpc_gp* h, int B, const double* Z, const 
         const double *dZ = Z, *dS = Sigma;
         // few inputs (an MPC's nodes): [Z | Sigma] goes up and [mean .. dcov_dS] comes down through the pinned mirror, one copy each
         const size_t nOut = nM + nC + n1 + n2 + n3 + n4;
-        IoPack io;
-        CHK(io.begin(h, host, std::max(nZ + nS, nOut)));
-        if (io.on) {
+        ChunkIo io;                                     // (only for its packed-or-not decision and the pinned block)
+        CHK(io.begin(h, host, {std::max(nZ + nS, nOut)}));
+        if (io.packed()) {
             std::memcpy(h->io_pin, Z, nZ * sizeof(double));
             std::memcpy(h->io_pin + nZ, Sigma, nS * sizeof(double));
             HIPCHK(hipMemcpyAsync(bZ, h->io_pin, (nZ + nS) * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -569,7 +575,7 @@ extern "C" int gpmpc_predict_em_sens(gpmpc_gp* h, int B, const double* Z, const 
 #undef GPMPC_EM_SENS
             HIPCHK(hipGetLastError());
         }
-        if (io.on) {
+        if (io.packed()) {
             // (the upload has been consumed: every kernel above is ordered behind it on the stream, and this copy behind them)
             HIPCHK(hipMemcpyAsync(h->io_pin, bM, nOut * sizeof(double), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
@@ -621,21 +627,18 @@ extern "C" int gpmpc_covar(gpmpc_gp* h, int n, const double* Xnew, double* covar
         dZ = h->Z;
     }
     launch_crosscov(cx.stream, d, h->XT, h->ws.hyper, h->ws.alpha, dZ, h->KsT, h->meanT, nullptr, h->N, Np, n, Bp, Ny);
-    double *VT = nullptr, *C = nullptr, *R = nullptr;
-    HIPCHK(hipMalloc(&VT, (size_t)Ny * Bp * Np * sizeof(double)));
-    HIPCHK(hipMalloc(&C, (size_t)Ny * Bp * Bp * sizeof(double)));
-    GemmP p = gemm_base(cx);  // VT[j][i] = sum_k KsT[j][k] invL[i][k]
-    p.A = h->KsT; p.lda = Np; p.sA = (long)Bp * Np; p.a_mc = 0;
-    p.B = h->ws.Inv; p.ldb = Np; p.sB = (long)Np * Np; p.b_nc = 0; p.kflags = KB_LE_N;
-    p.C = VT; p.ldc = Np; p.sC = (long)Bp * Np;
-    p.M = Bp; p.N = Np; p.K = Np;
-    launch_gemm(p, Ny, cx.stream);
+    DevArena mem;                               // released on every way out
+    double* VT = mem.take<double>((size_t)Ny * Bp * Np);
+    double* C = mem.take<double>((size_t)Ny * Bp * Bp);
+    HIPCHK(mem.status);
+    launch_vt(cx, h->KsT, h->ws.Inv, VT, Bp, Np, Ny);
     {
         // One step of refinement with L itself: V += L^-1 (ks - L V).  A product with the explicitly inverted factor is
         // 2.5 ... 4 x (rms; single entries up to 50 x) further from the exact sf^2 - ks_i^T K^-1 ks_j than a triangular solve
         // with L when cond(K) ~ 1e6 (sn = 1e-2; numpy shows the same with an explicit inverse, profiles/var_error_scale.txt);
         // the residual against L brings the off-diagonal entries back to the solve's error.  Two more products, off the hot path.
-        HIPCHK(hipMalloc(&R, (size_t)Ny * Bp * Np * sizeof(double)));
+        double* R = mem.take<double>((size_t)Ny * Bp * Np);
+        HIPCHK(mem.status);
         HIPCHK(hipMemcpyAsync(R, h->KsT, (size_t)Ny * Bp * Np * sizeof(double), hipMemcpyDeviceToDevice, cx.stream));
         GemmP r = gemm_base(cx);  // R[j][i] = KsT[j][i] - sum_k VT[j][k] L[i][k]
         r.A = VT; r.lda = Np; r.sA = (long)Bp * Np; r.a_mc = 0;
@@ -643,25 +646,12 @@ extern "C" int gpmpc_covar(gpmpc_gp* h, int n, const double* Xnew, double* covar
         r.C = R; r.ldc = Np; r.sC = (long)Bp * Np;
         r.M = Bp; r.N = Np; r.K = Np; r.alpha = -1.0; r.beta = 1.0;
         launch_gemm(r, Ny, cx.stream);
-        GemmP u = gemm_base(cx);  // VT[j][i] += sum_k R[j][k] invL[i][k]
-        u.A = R; u.lda = Np; u.sA = (long)Bp * Np; u.a_mc = 0;
-        u.B = h->ws.Inv; u.ldb = Np; u.sB = (long)Np * Np; u.b_nc = 0; u.kflags = KB_LE_N;
-        u.C = VT; u.ldc = Np; u.sC = (long)Bp * Np;
-        u.M = Bp; u.N = Np; u.K = Np; u.beta = 1.0;
-        launch_gemm(u, Ny, cx.stream);
+        launch_vt(cx, R, h->ws.Inv, VT, Bp, Np, Ny, 1.0);       // VT[j][i] += sum_k R[j][k] invL[i][k]
     }
-    GemmP q = gemm_base(cx);  // C = -VT VT^T
-    q.A = VT; q.lda = Np; q.sA = (long)Bp * Np; q.a_mc = 0;
-    q.B = VT; q.ldb = Np; q.sB = (long)Bp * Np; q.b_nc = 0;
-    q.C = C; q.ldc = Bp; q.sC = (long)Bp * Bp;
-    q.M = Bp; q.N = Bp; q.K = Np; q.alpha = -1.0;
-    launch_gemm(q, Ny, cx.stream);
+    launch_neg_gram(cx, VT, C, Bp, Np, Ny);
     std::vector<double> tmp((size_t)Ny * Bp * Bp);
     HIPCHK(hipMemcpyAsync(tmp.data(), C, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    hipFree(VT);
-    hipFree(C);
-    hipFree(R);
     std::vector<double> out((size_t)Ny * n * n);
     for (int a = 0; a < Ny; ++a) {
         const double sf = h->hyper[(size_t)a * h->nh() + d];

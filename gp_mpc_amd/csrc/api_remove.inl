@@ -30,10 +30,11 @@ static bool remove_prefers_downdate(int N1, int Ny, const std::vector<int>& sort
 
 namespace {
 struct RemoveScratch {              // device scratch of one call; released on every way out
-    double *Et = nullptr, *G = nullptr, *V = nullptr, *tau = nullptr, *pL[2] = {nullptr, nullptr}, *pT[2] = {nullptr, nullptr};
+    DevArena mem;                   // owns Et .. rem below
+    double *Et = nullptr, *G = nullptr, *V = nullptr, *tau = nullptr;
     int *src = nullptr, *rem = nullptr;
+    double *pL[2] = {nullptr, nullptr}, *pT[2] = {nullptr, nullptr};   // intermediate factors: device block list (block_alloc)
     ~RemoveScratch() {
-        hipFree(Et); hipFree(G); hipFree(V); hipFree(tau); hipFree(src); hipFree(rem);
         for (int s = 0; s < 2; ++s) { block_free(pL[s]); block_free(pT[s]); }
     }
 };
@@ -158,13 +159,14 @@ extern "C" int gpmpc_remove(gpmpc_gp* h, int n, const int* idx) {
     RemoveScratch s;
     {
         const int NpA = round_up(N0 - std::min(n, REMOVE_W), 64);   // the largest result
-        const size_t xb = (size_t)Ny * REMOVE_W * NpA * sizeof(double);
-        HIPCHK(hipMalloc(&s.Et, xb));
-        HIPCHK(hipMalloc(&s.G, xb));
-        HIPCHK(hipMalloc(&s.V, (size_t)Ny * 64 * REMOVE_W * sizeof(double)));
-        HIPCHK(hipMalloc(&s.tau, (size_t)Ny * 64 * sizeof(double)));
-        HIPCHK(hipMalloc(&s.src, (size_t)NpA * sizeof(int)));
-        HIPCHK(hipMalloc(&s.rem, (size_t)REMOVE_W * sizeof(int)));
+        const size_t xb = (size_t)Ny * REMOVE_W * NpA;
+        s.Et = s.mem.take<double>(xb);
+        s.G = s.mem.take<double>(xb);
+        s.V = s.mem.take<double>((size_t)Ny * 64 * REMOVE_W);
+        s.tau = s.mem.take<double>((size_t)Ny * 64);
+        s.src = s.mem.take<int>((size_t)NpA);
+        s.rem = s.mem.take<int>((size_t)REMOVE_W);
+        HIPCHK(s.mem.status);
         for (int q = 0; q < std::min(passes - 1, 2); ++q) {
             const int NpQ = round_up(N0 - std::min(n, (q + 1) * REMOVE_W), 64);
             HIPCHK(block_alloc(&s.pL[q], (size_t)Ny * NpQ * NpQ * sizeof(double)));

@@ -87,8 +87,8 @@ static int rollout_impl(gpmpc_gp* h, int method, int T, const double* z0, const 
     bool done = false;
     if (moments) CHK(ensure_beta(h));        // lazily refreshed after a fit: must not hide inside (or be missing from) a captured loop
 #ifndef GPMPC_EMULATED
-    static const bool use_graph = !(getenv("GPMPC_ROLLOUT_GRAPH") && atoi(getenv("GPMPC_ROLLOUT_GRAPH")) == 0);
-    static const int graph_max_np = getenv("GPMPC_ROLLOUT_GRAPH_NP") ? atoi(getenv("GPMPC_ROLLOUT_GRAPH_NP")) : 2048;
+    static const bool use_graph = env_int("GPMPC_ROLLOUT_GRAPH", 1) != 0;
+    static const int graph_max_np = env_int("GPMPC_ROLLOUT_GRAPH_NP", 2048);
     if (use_graph && !h->prof.on && h->Np <= graph_max_np) {
         const std::vector<long> key = {method, T, fb ? 1 : 0, Nu, h->N, h->Np, Ny, d, h->mean_kind, h->mean_add ? 1 : 0, h->Bcap,
                                        (long)buf, (long)h->XT, (long)h->ws.hyper, (long)h->ws.alpha, (long)h->ws.Inv,
@@ -245,7 +245,7 @@ static int rollout_multi_impl(gpmpc_gp* h, int M, const int* methods, int T, con
     // 'ME' / 'TA' group then runs NEXT TO that product, MFMA-bound against HBM-bound), then their T steps -- while the 'ME' / 'TA'
     // group's T steps run on the main queue; the queues meet once, in front of the copy back.  (The exact moments are
     // VALU-bound, the batch streams L^-1.)  GPMPC_ROLLOUT_OVERLAP=0: one group after the other, step by step, on the main queue.
-    static const bool overlap_env = !(getenv("GPMPC_ROLLOUT_OVERLAP") && atoi(getenv("GPMPC_ROLLOUT_OVERLAP")) == 0);
+    static const bool overlap_env = env_int("GPMPC_ROLLOUT_OVERLAP", 1) != 0;
     // (only 'EM' has scratch of its own; the legacy methods form their cross-covariances in the buffers the 'ME' / 'TA' batch uses)
     const bool overlap = overlap_env && moments && nA > 0 && !cnt[GPMPC_OLD_ME] && !cnt[GPMPC_OLD_TA] && h->side_stream &&
                          h->stream == h->own_stream;

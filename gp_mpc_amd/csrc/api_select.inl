@@ -2,50 +2,28 @@
 // Concern: gpmpc_append_select -- greedy max-variance choice among candidate points (select_kernels.hpp), then gpmpc_append
 // of the chosen rows.
 // ------------------------------------------------------------------------------------------------
-namespace {
-struct SelectScratch {              // device scratch of one call; released on every way out, before the append allocates
-    double *VT = nullptr, *S = nullptr, *GT = nullptr, *dg = nullptr, *score = nullptr, *gain = nullptr;
-    int *sel = nullptr, *flags = nullptr;
-    ~SelectScratch() {
-        hipFree(VT); hipFree(S); hipFree(GT); hipFree(dg); hipFree(score); hipFree(gain); hipFree(sel); hipFree(flags);
-    }
-};
-}  // namespace
-
 // The selection alone: picks[0 .. kout), gains[0 .. kout).  Everything n x n stays on the device.
 static int select_greedy(gpmpc_gp* h, int n, const double* Xcand, int k, double min_gain, std::vector<int>& picks,
                          std::vector<double>& gains, int& kout) {
     CHK(ensure_scratch(h, n));
     const Ctx cx = h->cx();
     const int Np = h->Np, Ny = h->Ny, d = h->d, Bp = round_up(n, 64);
-    SelectScratch s;
-    HIPCHK(hipMalloc(&s.VT, (size_t)Ny * Bp * Np * sizeof(double)));
-    HIPCHK(hipMalloc(&s.S, (size_t)Ny * Bp * Bp * sizeof(double)));
-    HIPCHK(hipMalloc(&s.GT, (size_t)Ny * k * Bp * sizeof(double)));
-    HIPCHK(hipMalloc(&s.dg, (size_t)2 * Ny * Bp * sizeof(double)));
-    HIPCHK(hipMalloc(&s.score, (size_t)2 * Bp * sizeof(double)));
-    HIPCHK(hipMalloc(&s.gain, (size_t)k * sizeof(double)));
-    HIPCHK(hipMalloc(&s.sel, (size_t)k * sizeof(int)));
-    HIPCHK(hipMalloc(&s.flags, (size_t)(k + 2) * sizeof(int)));
-    // (plain pointers for the launches: a launch argument list must not hold the owning struct itself)
-    double *VT = s.VT, *S = s.S, *GT = s.GT, *dg = s.dg, *score = s.score, *dgain = s.gain;
-    int *dsel = s.sel, *flags = s.flags;
+    DevArena mem;                   // device scratch of this call; released on every way out, before the append allocates
+    double* VT = mem.take<double>((size_t)Ny * Bp * Np);
+    double* S = mem.take<double>((size_t)Ny * Bp * Bp);
+    double* GT = mem.take<double>((size_t)Ny * k * Bp);
+    double* dg = mem.take<double>((size_t)2 * Ny * Bp);
+    double* score = mem.take<double>((size_t)2 * Bp);
+    double* dgain = mem.take<double>((size_t)k);
+    int* dsel = mem.take<int>((size_t)k);
+    int* flags = mem.take<int>((size_t)(k + 2));
+    HIPCHK(mem.status);
     HIPCHK(hipMemsetAsync(flags, 0, (size_t)(k + 2) * sizeof(int), cx.stream));
     HIPCHK(hipMemcpyAsync(h->Z, Xcand, (size_t)n * d * sizeof(double), hipMemcpyHostToDevice, cx.stream));
-    // S_a = k_a(C, C) - V^T V on the route of gpmpc_covar (api_predict.inl)
+    // S_a = k_a(C, C) - V^T V on the route of gpmpc_covar (api_predict.inl), without its refinement step
     launch_crosscov(cx.stream, d, h->XT, h->ws.hyper, h->ws.alpha, h->Z, h->KsT, h->meanT, nullptr, h->N, Np, n, Bp, Ny);
-    GemmP p = gemm_base(cx);  // VT[j][i] = sum_k KsT[j][k] invL[i][k]
-    p.A = h->KsT; p.lda = Np; p.sA = (long)Bp * Np; p.a_mc = 0;
-    p.B = h->ws.Inv; p.ldb = Np; p.sB = (long)Np * Np; p.b_nc = 0; p.kflags = KB_LE_N;
-    p.C = VT; p.ldc = Np; p.sC = (long)Bp * Np;
-    p.M = Bp; p.N = Np; p.K = Np;
-    launch_gemm(p, Ny, cx.stream);
-    GemmP q = gemm_base(cx);  // S = -VT VT^T
-    q.A = VT; q.lda = Np; q.sA = (long)Bp * Np; q.a_mc = 0;
-    q.B = VT; q.ldb = Np; q.sB = (long)Bp * Np; q.b_nc = 0;
-    q.C = S; q.ldc = Bp; q.sC = (long)Bp * Bp;
-    q.M = Bp; q.N = Bp; q.K = Np; q.alpha = -1.0;
-    launch_gemm(q, Ny, cx.stream);
+    launch_vt(cx, h->KsT, h->ws.Inv, VT, Bp, Np, Ny);
+    launch_neg_gram(cx, VT, S, Bp, Np, Ny);
     hipLaunchKernelGGL(select_schur_kernel, dim3((Bp + 255) / 256, Bp, Ny), dim3(256), 0, cx.stream, h->Z, h->ws.hyper, S, n, Bp, d);
     hipLaunchKernelGGL(select_init_kernel, dim3((Bp + 255) / 256), dim3(256), 0, cx.stream, S, dg, score, n, Bp, Ny);
     for (int t = 0; t < k; ++t)

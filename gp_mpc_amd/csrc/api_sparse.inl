@@ -15,11 +15,10 @@
 // ------------------------------------------------------------------------------------------------
 namespace {
 struct FitcScratch {                // device scratch of one build and the handle under construction; released on every way out
-    double *VT = nullptr, *ys = nullptr, *Bm = nullptr, *r = nullptr, *hyp = nullptr;
+    DevArena mem;                   // VT, ys, Bm, r, hyp of fitc_build
     Workspace tw;                   // M-sized workspace of the two factorisations (B, the reversed P)
     gpmpc_gp* s = nullptr;
     ~FitcScratch() {
-        hipFree(VT); hipFree(ys); hipFree(Bm); hipFree(r); hipFree(hyp);
         ws_free(tw);
         if (s) {
             const std::string keep = g_err;
@@ -58,14 +57,13 @@ static int fitc_build(gpmpc_gp* h, gpmpc_gp* s, FitcScratch& sc, const std::vect
     CHK(ensure_scratch(s, std::min(N, chunk)));
     const int Bcp = round_up(std::min(N, chunk), 64);
     const Ctx cx = s->cx();
-    HIPCHK(hipMalloc(&sc.VT, (size_t)Ny * Bcp * Mp * sizeof(double)));
-    HIPCHK(hipMalloc(&sc.ys, (size_t)Ny * Bcp * sizeof(double)));
-    HIPCHK(hipMalloc(&sc.Bm, (size_t)Ny * sM * sizeof(double)));
-    HIPCHK(hipMalloc(&sc.r, (size_t)Ny * Mp * sizeof(double)));
-    HIPCHK(hipMalloc(&sc.hyp, (size_t)Ny * (d + 2) * sizeof(double)));
+    double* VT = sc.mem.take<double>((size_t)Ny * Bcp * Mp);
+    double* ys = sc.mem.take<double>((size_t)Ny * Bcp);
+    double* Bm = sc.mem.take<double>((size_t)Ny * sM);
+    double* r = sc.mem.take<double>((size_t)Ny * Mp);
+    double* hyp = sc.mem.take<double>((size_t)Ny * (d + 2));
+    HIPCHK(sc.mem.status);
     CHK(ws_alloc(sc.tw, Ny, Mp, d));
-    // (plain pointers for the launches: a launch argument list must not hold the owning struct itself)
-    double *VT = sc.VT, *ys = sc.ys, *Bm = sc.Bm, *r = sc.r, *hyp = sc.hyp;
     Workspace& tw = sc.tw;
     HIPCHK(hipMemcpyAsync(hyp, hy.data(), (size_t)Ny * (d + 2) * sizeof(double), hipMemcpyHostToDevice, cx.stream));
     HIPCHK(hipMemsetAsync(r, 0, (size_t)Ny * Mp * sizeof(double), cx.stream));
@@ -76,12 +74,7 @@ static int fitc_build(gpmpc_gp* h, gpmpc_gp* s, FitcScratch& sc, const std::vect
         hipLaunchKernelGGL(fitc_gather_kernel, dim3((nc * d + 255) / 256), dim3(256), 0, cx.stream, (const double*)h->XT, s->Z, NpS,
                            c0, nc, d);
         launch_crosscov(cx.stream, d, s->XT, s->ws.hyper, s->ws.alpha, s->Z, s->KsT, s->meanT, nullptr, M, Mp, nc, Bp, Ny);
-        GemmP p = gemm_base(cx);  // VT[c][m] = sum_k KsT[c][k] Luu^-1[m][k]
-        p.A = s->KsT; p.lda = Mp; p.sA = (long)Bp * Mp; p.a_mc = 0;
-        p.B = s->ws.Inv; p.ldb = Mp; p.sB = sM; p.b_nc = 0; p.kflags = KB_LE_N;
-        p.C = VT; p.ldc = Mp; p.sC = (long)Bp * Mp;
-        p.M = Bp; p.N = Mp; p.K = Mp;
-        launch_gemm(p, Ny, cx.stream);
+        launch_vt(cx, s->KsT, s->ws.Inv, VT, Bp, Mp, Ny);   // VT[c][m] = sum_k KsT[c][k] Luu^-1[m][k]
         hipLaunchKernelGGL(fitc_scale_kernel, dim3(Bp / 4, Ny), dim3(256), 0, cx.stream, VT, (const double*)h->Y, (const double*)hyp,
                            ys, c0, nc, Bp, M, Mp, NpS, d);
         PhaseTimer t(s, GPMPC_PH_VARGEMM);                  // (profiling follows the source handle: gpmpc_sparse_fitc below)

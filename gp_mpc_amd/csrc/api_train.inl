@@ -413,7 +413,7 @@ static int nll_batch(gpmpc_gp* h, int a, std::vector<NllReq*>& reqs, bool retain
             const int n = (int)std::min<size_t>(cap, G.size() - b0);
             std::vector<int> failed;
             const auto t0 = std::chrono::steady_clock::now();
-            static const bool skip_inv = !(getenv("GPMPC_TRAIN_SKIP_INVERSE") && atoi(getenv("GPMPC_TRAIN_SKIP_INVERSE")) == 0);
+            static const bool skip_inv = env_int("GPMPC_TRAIN_SKIP_INVERSE", 1) != 0;
             const bool vonly = wg == 0 && retain && skip_inv && G.size() <= (size_t)cap;
             CHK(nll_batch_core(h, a, n, &G[b0], wg == 1, 0.0, failed, vonly));
             const int inv_first = h->lock_inv_panels;   // what this pass left in Inv (one value for the whole batch workspace)
@@ -594,14 +594,14 @@ extern "C" int gpmpc_train_multistart(gpmpc_gp* h, int nstart, const double* sta
         }
         // Lock-step: the restarts of this rank advance together and their evaluation points form batches (above).  `nstart`
         // is the same on every rank, so the choice is too.  GPMPC_TRAIN_LOCKSTEP=0 / a single restart: one after the other.
-        static const bool lockstep_env = !(getenv("GPMPC_TRAIN_LOCKSTEP") && atoi(getenv("GPMPC_TRAIN_LOCKSTEP")) == 0);
+        static const bool lockstep_env = env_int("GPMPC_TRAIN_LOCKSTEP", 1) != 0;
         if (lockstep_env && nstart > 1 && !mine.empty() && local_rc == GPMPC_OK) {
             LockstepPool pool;
             pool.n_threads = (int)mine.size();
             pool.slots.resize(mine.size());
             // value-only trials with the gradient of the accepted point from its retained factors: when this rank's restarts
             // fit one batch (GPMPC_TRAIN_RETAIN=0: every trial with its gradient, as when they do not fit)
-            static const bool retain_env = !(getenv("GPMPC_TRAIN_RETAIN") && atoi(getenv("GPMPC_TRAIN_RETAIN")) == 0);
+            static const bool retain_env = env_int("GPMPC_TRAIN_RETAIN", 1) != 0;
             bool retain = false;
             if (retain_env) {
                 const int erc = ensure_batch_ws(h, (int)mine.size());

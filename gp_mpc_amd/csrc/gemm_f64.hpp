@@ -46,6 +46,12 @@
 
 namespace gpmpc {
 
+// integer knob from the environment: atoi of `name` when it is set, `def` otherwise
+inline int env_int(const char* name, int def) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : def;
+}
+
 // raw buffer resource over [base, base + bytes): loads beyond the range return 0 (gfx9 family word 3: 0x00020000)
 #ifdef GPMPC_EMULATED
 struct gpmpc_rsrc_t { const char* base; unsigned bytes; };
@@ -388,10 +394,10 @@ inline int gemm_pick_tile(const GemmP& p, int batch) {
         const long b = (long)((p.M + t - 1) / t) * ((p.N + t - 1) / t) * batch;
         return p.lower ? (b + 1) / 2 : b;
     };
-    static const int t128 = getenv("GPMPC_T128") ? atoi(getenv("GPMPC_T128")) : 512;
+    static const int t128 = env_int("GPMPC_T128", 512);
     // (r03: 256 instead of 512: -14 us on the C2 inverse tail with the DMA-staged 64-row kernel; r04, with the prediction running
     //  behind the tail: 384 / 512 instead of 256: -35 / -30 us per C2 step, C3 and C4 unchanged -- tools/gpu_r04_s.sh)
-    static const int t64 = getenv("GPMPC_T64") ? atoi(getenv("GPMPC_T64")) : 384;
+    static const int t64 = env_int("GPMPC_T64", 384);
     if (p.N <= 32 || p.M <= 32) return 32;     // skinny products (a handful of prediction points)
     // A triangular operand makes the heaviest tile K / 128 slabs long while the average is half that: unless the
     // average work per workgroup slot (512 of them) reaches the heaviest tile, the heaviest tiles alone set the time
@@ -439,11 +445,11 @@ inline void launch_gemm_cfg(GemmP p, int batch, hipStream_t stream, int resident
     // XCD-consistent column residues (pad the grid width to a multiple of 8) cut the fetched bytes of the
     // variance GEMM by 27 % (3.33 -> 2.43 GB raw FETCH_SIZE) but cost 1-3 % time on every shape measured
     // (the kernels are MFMA-issue bound, not L2 bound): off by default, GPMPC_PAD_MIN=<tiles> enables it.
-    static const int pad_min = getenv("GPMPC_PAD_MIN") ? atoi(getenv("GPMPC_PAD_MIN")) : (1 << 30);
+    static const int pad_min = env_int("GPMPC_PAD_MIN", 1 << 30);
     p.npad = (p.tilesNe >= pad_min) ? ((p.tilesNe + 7) & ~7) : p.tilesNe;
     dim3 grid(p.remap ? prows * pcols * 64 : p.tilesMe * p.npad, 1, batch);
     const dim3 block(64 * WGM * WGN);
-    static const bool use_buf = !(getenv("GPMPC_GEMM_BUF") && atoi(getenv("GPMPC_GEMM_BUF")) == 0);
+    static const bool use_buf = env_int("GPMPC_GEMM_BUF", 1) != 0;
     const bool small = (long)p.M * p.lda * 8 < (1L << 32) && (long)p.N * p.ldb * 8 < (1L << 32);
     if (!p.a_mc && !p.b_nc && use_buf && small)
         hipLaunchKernelGGL((gemm_f64_kernel<BM, BN, BK, WGM, WGN, false, false, GPMPC_GEMM_SPLIT, true>), grid, block, 0,

@@ -309,7 +309,7 @@ inline void launch_gemm_dma(GemmP p, int batch, hipStream_t stream, int resident
     // workgroups go round-robin to the 8 XCDs, so every XCD then keeps seeing the same B panels in its own L2).  With
     // the register-staged kernel this cost 1-3 % (gemm_f64.hpp); with the DMA-staged one it gains 0.5 % on the
     // variance GEMM and on the step.  GPMPC_PAD_MIN=<tiles> moves the threshold.
-    static const int pad_min = getenv("GPMPC_PAD_MIN") ? atoi(getenv("GPMPC_PAD_MIN")) : 16;
+    static const int pad_min = env_int("GPMPC_PAD_MIN", 16);
     p.npad = (p.tilesNe >= pad_min) ? ((p.tilesNe + 7) & ~7) : p.tilesNe;
     const dim3 grid(p.tilesMe * p.npad, 1, batch);
     if (!p.a_mc && !p.b_nc) launch_gemm_dma_kernel<BM, BN, WGM, WGN, STAGES, WPS, false, false>(p, grid, stream);
@@ -325,7 +325,7 @@ inline int launch_gemm(const GemmP& p, int batch, hipStream_t stream, int force_
     const int tile = force_tile ? force_tile : g_gemm_force_tile ? g_gemm_force_tile : gemm_pick_tile(p, batch);
     // GPMPC_GEMM_DMA: bit 0 the 128 x 128 tile, bit 1 the 64 x 64 tile, bit 2 the 32 x 32 tile (four-image ring: the
     // latency-bound small products of the inverse tree, -18 us on the C2 fit) through the DMA-staged kernel; default all
-    static const int use_dma = getenv("GPMPC_GEMM_DMA") ? atoi(getenv("GPMPC_GEMM_DMA")) : 7;
+    static const int use_dma = env_int("GPMPC_GEMM_DMA", 7);
     if (tile == 128 && (use_dma & 1) && gemm_dma_supported(p)) {
         launch_gemm_dma<128, 128, 2, 4, 2, 4>(p, batch, stream, 512);
     } else if (tile == 128) {
@@ -334,7 +334,7 @@ inline int launch_gemm(const GemmP& p, int batch, hipStream_t stream, int force_
         // long K (the products of the inverse tree): three slab images; short K (the K = 64 updates of the flagged
         // factorisation, bound by their C traffic): two, so that more workgroups fit a CU  (C2 fit -15 us with three,
         // C3 fit +8 ms with three everywhere)
-        static const int st64 = getenv("GPMPC_T64_STAGES") ? atoi(getenv("GPMPC_T64_STAGES")) : 0;
+        static const int st64 = env_int("GPMPC_T64_STAGES", 0);
         if (st64 == 3 || (st64 == 0 && p.K >= 256)) launch_gemm_dma<64, 64, 2, 2, 3, 4>(p, batch, stream, 1024);
         else launch_gemm_dma<64, 64, 2, 2, 2, 4>(p, batch, stream, 1024);
     } else if (tile == 64) {

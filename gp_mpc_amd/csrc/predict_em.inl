@@ -48,12 +48,12 @@ static int predict_moments_chunk(gpmpc_gp* h, int method, int B, const double* d
         const int P = Ny * (Ny + 1) / 2, tiles = Np / 64;
         // column tiles per workgroup of the pair sums (em_kernels.hpp; GPMPC_EM_CHUNK, tuning aid; >= tiles: one workgroup per strip)
         // (also gpmpc_set_tuning("em_chunk", n): the tests sweep it at small sizes)
-        static const int em_chunk_env = getenv("GPMPC_EM_CHUNK") ? atoi(getenv("GPMPC_EM_CHUNK")) : 64;   // (C3: 64 -> 38.4 ms, 32 -> 39.4, 16 -> 42.5, whole strips 39.9: profiles/r05_em_chunk_ab.txt)
+        static const int em_chunk_env = env_int("GPMPC_EM_CHUNK", 64);   // (C3: 64 -> 38.4 ms, 32 -> 39.4, 16 -> 42.5, whole strips 39.9: profiles/r05_em_chunk_ab.txt)
         const int em_chunk = std::max(1, std::min(g_em_chunk > 0 ? g_em_chunk : em_chunk_env, tiles)), nstrip = tiles * ((tiles + em_chunk - 1) / em_chunk);
         // The a == b launch on a balanced schedule (em_diag_kernel): the pair's triangle of tiles in `diag_segs` equal ranges.
         // GPMPC_EM_DIAG_SEGS / gpmpc_set_tuning("em_diag_segs", n): 0 = strips and chunks as r05 (em_pair2_kernel<true>), n > 0 =
         // that many ranges per pair.  nslots = partial sums per pair (both launches write all of them).
-        static const int diag_segs_env = getenv("GPMPC_EM_DIAG_SEGS") ? atoi(getenv("GPMPC_EM_DIAG_SEGS")) : -1;
+        static const int diag_segs_env = env_int("GPMPC_EM_DIAG_SEGS", -1);
         const long tri = (long)tiles * (tiles + 1) / 2;
         const int diag_want = g_em_diag_segs >= 0 ? g_em_diag_segs : diag_segs_env >= 0 ? diag_segs_env : em_diag_default_segs(g_cu_count[h->device], Ny, tri);
         // (em_diag_kernel addresses K^-1 by a 32-bit element offset: from Np^2 >= 2^32 on -- 34 GB per K^-1 -- the a == b pairs
@@ -75,7 +75,7 @@ static int predict_moments_chunk(gpmpc_gp* h, int method, int B, const double* d
         // captured-graph range the a == b launch -- the one that streams K^-1 -- goes to the inverse queue NEXT TO the other
         // (GPMPC_EM_PAIR_OVERLAP=0: one after the other, as r01-r05), and in front of it, next to the operands kernel, the mean
         // (it needs the prepared matrices only; the covariance's last kernel waits for that queue anyway).
-        static const bool pair_overlap_env = !(getenv("GPMPC_EM_PAIR_OVERLAP") && atoi(getenv("GPMPC_EM_PAIR_OVERLAP")) == 0);
+        static const bool pair_overlap_env = env_int("GPMPC_EM_PAIR_OVERLAP", 1) != 0;
         const bool pair_overlap = pair_overlap_env && dCov && h->aux_stream && Np > 2048 && Ny > 1;
         hipStream_t diag_q = pair_overlap ? h->aux_stream : cx.stream;
         if (pair_overlap) {
@@ -92,7 +92,7 @@ static int predict_moments_chunk(gpmpc_gp* h, int method, int B, const double* d
         // (with the covariance the chunk sums of the mean are added up by em_finish_kernel)
         // exp of the pair sums: GPMPC_EM_PAIR (tuning aid) 1 (default) the 2^(j / 2048) table, 2 the conflict-free 32-entry table,
         // 3 the polynomial exp_lean (r05, C3, same box: 40.8 / 43.3 / 46.3 ms per step; r04's kernel 45.7)
-        static const int pair_form = getenv("GPMPC_EM_PAIR") ? atoi(getenv("GPMPC_EM_PAIR")) : 1;
+        static const int pair_form = env_int("GPMPC_EM_PAIR", 1);
         const double* etab = g_exp_tab[h->device];
 #define GPMPC_EM_PAIR2(KDV, TABV)                                                                                                     \
         if (pair_overlap) {                                                                                                           \

@@ -976,7 +976,7 @@ def check_sensitivities(lib, g, nprobe=12):
 
 
 def check_io_pack_boundary(lib, N=100, d=3, Ny=2, seed=51):
-    """Host-pointer calls stage small argument sets through one pinned block (IoPack, gpmpc_api.hip: 32768 doubles); just
+    """Host-pointer calls stage small argument sets through one pinned block (ChunkIo, api_predict.inl: 32768 doubles); just
     below and just above that size the same call takes the two copy routes and must give the same numbers, and both
     must match the oracle."""
     B1, B2 = 1300, 1400            # 'TA' with J: 24 doubles per point (+ padding) -> the limit falls near B = 1365
@@ -2974,6 +2974,101 @@ def check_chunked_device_pointers(lib, fill=-7.25):
         h.set_pointer_mode(False)
         lib.set_tuning('predict_chunk', 0)
         for a in [z, s, sm] + outs:
+            a.free()
+
+
+def check_sens_device_pointers(lib, fill=-7.25):
+    """gpmpc_predict_sens in device-pointer mode, 64 points per chunk, B = 165 (chunks 64, 64, 37): all five outputs, then
+    without Hm, then without dvar -- the sensitivity kernel writes both, so the one left out lands in the handle's staging.
+    Outputs are 64 points too long and pre-filled: the head holds the bits of the host-pointer call, the tail is untouched."""
+    mdl = chunk_model(lib)
+    h, B, d, Ny = mdl.h, mdl.B, mdl.d, mdl.Ny
+    names = ('mean', 'var', 'J', 'Hm', 'dvar')
+    shapes = ((Ny,), (Ny,), (Ny, d), (Ny, d, d), (Ny, d))
+    z = DevArray(lib, mdl.Z)
+    made = []
+    try:
+        lib.set_tuning('predict_chunk', 64)
+        host = h.predict_sens(mdl.Z)
+        h.set_pointer_mode(True)
+        for skip in (None, 'Hm', 'dvar'):
+            outs = [None if nm == skip else DevArray(lib, np.full((B + 64,) + sh, fill)) for nm, sh in zip(names, shapes)]
+            made += [o for o in outs if o is not None]
+            h.predict_sens_dev(B, z.ptr, *[None if o is None else o.ptr for o in outs])
+            h.synchronize()
+            for nm, o, want in zip(names, outs, host):
+                if o is None:
+                    continue
+                got = o.numpy()
+                assert np.all(got[B:] == fill), (skip, nm, 'wrote past the end')
+                assert np.array_equal(got[:B], want), (skip, nm, np.argwhere(got[:B] != want)[:4].tolist())
+    finally:
+        h.set_pointer_mode(False)
+        lib.set_tuning('predict_chunk', 0)
+        for a in [z] + made:
+            a.free()
+
+
+def check_sens_unpacked_host(lib, B=1000, c=250, n=100):
+    """gpmpc_predict_sens with host pointers beyond the packed block: at d = 3, Ny = 2 a point carries 37 doubles, so
+    B = 1000 in ONE chunk (no 'predict_chunk' cap) exceeds the 32768 doubles and every array goes up or down in a copy of its
+    own.  Same bits as the calls on slices of 250 points, which go packed; the first 100 points against the oracle with the
+    bars of check_sensitivities_batches."""
+    mdl = chunk_model(lib, B=B)
+    assert B * (mdl.d + mdl.Ny * (2 + 2 * mdl.d + mdl.d * mdl.d)) > 32768 >= c * (mdl.d + 1 + mdl.Ny * (2 + 2 * mdl.d + mdl.d * mdl.d))
+    mean, var, J, Hm, dvar = same_bits_as_slices(mdl.h.predict_sens, c, mdl.Z, tag='sens, unpacked')
+    oH, odv = go.mean_var_sens(mdl.Z[:n], mdl.X, mdl.H, mdl.f['alpha'], mdl.f['chol'])
+    mdl.mean_var_bars(mean[:n], var[:n])
+    mdl.jac_bars(J[:n])
+    assert np.max(np.abs(Hm[:n] - oH) / (mdl.ms[:n] / mdl.ell_min ** 2)[..., None, None]) <= 1e-10
+    assert np.max(np.abs(dvar[:n] - odv) / (mdl.sf2 / mdl.ell_min)[None, :, None]) <= 1e-10, np.max(np.abs(dvar[:n] - odv))
+
+
+def check_covar_device_pointers(lib, n=70):
+    """gpmpc_covar in device-pointer mode (candidates read in place, the result copied into the caller's device array),
+    n = 70: the bits of the host-pointer call."""
+    mdl = chunk_model(lib)
+    h = mdl.h
+    host = h.covar(mdl.Z[:n])
+    x, out = DevArray(lib, mdl.Z[:n]), DevArray(lib, np.zeros((mdl.Ny, n, n)))
+    try:
+        h.set_pointer_mode(True)
+        h.covar_dev(n, x.ptr, out.ptr)
+        h.synchronize()
+        got = out.numpy()
+        assert np.array_equal(got, host), np.argwhere(got != host)[:4].tolist()
+    finally:
+        h.set_pointer_mode(False)
+        x.free()
+        out.free()
+
+
+def check_mean_var_null_outputs(lib):
+    """gpmpc_predict_mean_var with `mean` NULL and with `var` NULL, host pointers at B = 5 and device pointers at B = 70: the
+    output that is there carries the bits it has when both are requested."""
+    mdl = chunk_model(lib)
+    h, Ny = mdl.h, mdl.Ny
+    Z5 = np.ascontiguousarray(mdl.Z[:5])
+    m, v = h.predict_mean_var(Z5)
+    m1, v1 = np.zeros_like(m), np.zeros_like(v)
+    h.predict_mean_var_dev(5, Z5, None, v1)
+    h.predict_mean_var_dev(5, Z5, m1, None)
+    assert np.array_equal(v1, v) and np.array_equal(m1, m)
+    B = 70
+    z = DevArray(lib, mdl.Z[:B])
+    outs = [DevArray(lib, np.zeros((B, Ny))) for _ in range(4)]
+    try:
+        h.set_pointer_mode(True)
+        h.predict_mean_var_dev(B, z.ptr, outs[0].ptr, outs[1].ptr)
+        h.predict_mean_var_dev(B, z.ptr, None, outs[2].ptr)
+        h.predict_mean_var_dev(B, z.ptr, outs[3].ptr, None)
+        h.synchronize()
+        mb, vb, v2, m2 = [o.numpy() for o in outs]
+        mdl.mean_var_bars(mb, vb)
+        assert np.array_equal(v2, vb) and np.array_equal(m2, mb)
+    finally:
+        h.set_pointer_mode(False)
+        for a in [z] + outs:
             a.free()
 
 

@@ -181,7 +181,7 @@ def test_every_environment_switch_is_documented():
     names = set()
     for fn in os.listdir(csrc):
         if fn.endswith(('.inl', '.hpp', '.hip')):
-            names |= set(re.findall(r'getenv\("(GPMPC_[A-Z0-9_]+)"\)', open(os.path.join(csrc, fn)).read()))
+            names |= set(re.findall(r'(?:getenv|env_int)\("(GPMPC_[A-Z0-9_]+)"', open(os.path.join(csrc, fn)).read()))
     assert len(names) > 40, len(names)
     doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
     missing = sorted(n for n in names if n not in doc)

@@ -406,5 +406,21 @@ def test_emu_covar_chunks(emu):
     pc.check_covar_chunks(emu)
 
 
+def test_emu_sens_device_pointers(emu):
+    pc.check_sens_device_pointers(emu)
+
+
+def test_emu_sens_unpacked_host(emu):
+    pc.check_sens_unpacked_host(emu)
+
+
+def test_emu_covar_device_pointers(emu):
+    pc.check_covar_device_pointers(emu)
+
+
+def test_emu_mean_var_null_outputs(emu):
+    pc.check_mean_var_null_outputs(emu)
+
+
 def test_emu_chunk_routing(emu):
     pc.check_chunk_routing(emu, N=700, d=3, B=200)       # the first shape of test_emu_fused_fit_predict

@@ -479,6 +479,22 @@ def test_covar_chunks(lib):
     pc.check_covar_chunks(lib)
 
 
+def test_sens_device_pointers(lib):
+    pc.check_sens_device_pointers(lib)
+
+
+def test_sens_unpacked_host(lib):
+    pc.check_sens_unpacked_host(lib)
+
+
+def test_covar_device_pointers(lib):
+    pc.check_covar_device_pointers(lib)
+
+
+def test_mean_var_null_outputs(lib):
+    pc.check_mean_var_null_outputs(lib)
+
+
 def test_chunk_routing(lib):
     pc.check_chunk_routing(lib, N=700, d=3, B=200)
 
