@@ -36,6 +36,8 @@ struct gpmpc_gp {
     long n_behind_tail = 0;                              // predictions that started next to a fit's tail (predict_behind_tail)
     long n_remove_down = 0, n_remove_refit = 0;          // gpmpc_remove calls that downdated the factors / that refitted
     long train_iters = 0, train_evals = 0;              // of the last gpmpc_train_multistart (this rank's restarts)
+    long train_retained = 0;                            // ... points whose gradient came from retained factors (nll_grad_retained)
+    long train_jitter = 0;                              // ... points a lock-step batch repeated with the 1e-8 jitter
     double train_flop = 0.0;                            // ... and its algorithmic matrix flops: N^3/3 per Cholesky, per L^-1, per K^-1 lower triangle
     int nll_last_a = -1;                                 // the training workspace holds the factors of this output ...
     std::vector<double> nll_last_row;                    // ... at these hyper-parameters (gpmpc_nll; nll_grad_last reuses them)
@@ -416,6 +418,8 @@ int gpmpc_get_counter(gpmpc_gp* h, const char* name, long* value) {
     else if (std::strcmp(name, "remove_refits") == 0) *value = h->n_remove_refit;
     else if (std::strcmp(name, "train_iterations") == 0) *value = h->train_iters;
     else if (std::strcmp(name, "train_evaluations") == 0) *value = h->train_evals;
+    else if (std::strcmp(name, "train_retained_gradients") == 0) *value = h->train_retained;
+    else if (std::strcmp(name, "train_jitter_repeats") == 0) *value = h->train_jitter;
     else if (std::strcmp(name, "workspace_blocks_reused") == 0 || std::strcmp(name, "workspace_blocks_fresh") == 0) {
         std::lock_guard<std::mutex> lk(g_block_mutex);
         *value = std::strcmp(name, "workspace_blocks_reused") == 0 ? g_block_reuses : g_block_fresh;

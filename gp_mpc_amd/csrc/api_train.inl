@@ -331,6 +331,7 @@ static int nll_grad_retained(gpmpc_gp* h, int a, const std::vector<NllReq*>& G, 
     cx.no_workers = true;
     HIPCHK(hipMemcpyAsync(h->bzmap, pos.data(), m * sizeof(int), hipMemcpyHostToDevice, h->stream));
     h->train_flop += m * ((double)h->N * h->N * h->N / 3.0) * (h->lock_inv_panels > 0 ? 2.0 : 1.0);   // (L^-1 now) + K^-1
+    h->train_retained += m;
     if (h->lock_inv_panels > 0) {                 // the value batch stopped at L and the diagonal blocks' inverses
         PhaseTimer t(h, GPMPC_PH_FACTOR);
         twolevel_inverse_all(cx, ws, cx.stream, h->lock_inv_panels, m, h->bzmap);
@@ -428,6 +429,7 @@ static int nll_batch(gpmpc_gp* h, int a, std::vector<NllReq*>& reqs, bool retain
                 std::vector<NllReq*> again;
                 for (int i : failed) again.push_back(G[b0 + i]);
                 std::vector<int> failed2;
+                h->train_jitter += (long)again.size();
                 CHK(nll_batch_core(h, a, (int)again.size(), again.data(), wg == 1, 1e-8, failed2, vonly));
                 // the repeat may have taken another execution than the first pass (a hand-off time-out, a parked chain): the
                 // slots then hold two kinds of Inv and h->lock_inv_panels describes only the repeat's -- retain nothing,
@@ -544,6 +546,7 @@ extern "C" int gpmpc_train_multistart(gpmpc_gp* h, int nstart, const double* sta
     std::string local_err;
     long iters_total = 0, evals_total = 0;
     h->train_flop = 0.0;
+    h->train_retained = h->train_jitter = 0;
     for (int a = 0; a < Ny && local_rc == GPMPC_OK; ++a) {
         BoxProblem P;
         P.n = nh;

@@ -40,6 +40,9 @@ struct BoxResult {
     bool ok = false;
 };
 
+// (tests/train_replay_cases.py holds a line-by-line Python port of this function and of run_restart in api_train.inl; the
+//  training tests replay the search on the oracle with it.  A change of the arithmetic or of the order of evaluations here
+//  has to be made there as well.)
 inline BoxResult minimize_box_lbfgs(const BoxProblem& P, const double* theta0, int max_iter, double tol) {
     const int n = P.n, M = 8;
     const double inf = std::numeric_limits<double>::infinity();

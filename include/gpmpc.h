@@ -329,7 +329,12 @@ int gpmpc_nll(gpmpc_gp* h, int a, const double* hyper_row, double* nll, double* 
  * accepted step always lowers the NLL; the L-BFGS memory is dropped when the set of bound-pinned variables changes.
  * optimizer_opts written for IPOPT / SLSQP have no counterpart here: only max_iter and tol exist.  Iteration and
  * evaluation totals of the last call (this rank's restarts, both stages): gpmpc_get_counter "train_iterations" /
- * "train_evaluations", and "train_gflop" = its algorithmic matrix work (N^3/3 per Cholesky, per L^-1 formed, per K^-1).  starts[Ny x nstart x W] (W =
+ * "train_evaluations", and "train_gflop" = its algorithmic matrix work (N^3/3 per Cholesky, per L^-1 formed, per K^-1).
+ * Which route the lock-step search of the last call took, reset by every call like the totals above:
+ * "train_retained_gradients" = points whose gradient was formed from the factors a value-only batch had left behind
+ * (0 when this rank's restarts do not fit one batch, and with a single restart); "train_jitter_repeats" = points that a
+ * lock-step batch evaluated a second time with the 1e-8 jitter (the single-restart route reports its jitter through
+ * gpmpc_nll's jitter_out and does not count here).  starts[Ny x nstart x W] (W =
  * gpmpc_hyper_width): one initial point per restart -- the reference starts every restart from the same point
  * (optimize.py:462-466, its Latin-hypercube line :218 is commented out); lb, ub[Ny x W]: the box (optimize.py:434-443 or
  * :204-229; +-HUGE_VAL for none).  For every output the restart with the smallest NLL wins (first minimum, np.argmin
