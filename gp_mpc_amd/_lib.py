@@ -495,14 +495,22 @@ class Handle:
                                                        _ptr(dvar)))
         return mean, var, J, Hm, dvar
 
-    def predict_em_sens(self, Z, Sigma, want_cov=True):
+    EM_SENS_OUTPUTS = ('mean', 'cov', 'dmean_dz', 'dmean_dS', 'dcov_dz', 'dcov_dS')
+
+    def predict_em_sens(self, Z, Sigma, want_cov=True, outputs=None):
         """'EM' value and Jacobians: mean[B,Ny], cov[B,Ny,Ny], dmean_dz[B,Ny,d], dmean_dS[B,Ny,d,d],
         dcov_dz[B,Ny,Ny,d], dcov_dS[B,Ny,Ny,d,d].  want_cov=False: cov is None and its pair sums (a quarter of the
-        call) are not formed -- what a Jacobian callback wants."""
+        call) are not formed -- what a Jacobian callback wants.  outputs: the names (EM_SENS_OUTPUTS) of the arrays to
+        request; every other one is passed as NULL and returned as None (default: all six, less cov without want_cov)."""
         Z = _f64(Z).reshape(-1, self.d)
         B, d, Ny = Z.shape[0], self.d, self.Ny
         Sigma = _f64(Sigma).reshape(B, d, d)
         out = [np.zeros(sh) for sh in ((B, Ny), (B, Ny, Ny), (B, Ny, d), (B, Ny, d, d), (B, Ny, Ny, d), (B, Ny, Ny, d, d))]
+        if outputs is not None:
+            unknown = set(outputs) - set(self.EM_SENS_OUTPUTS)
+            if unknown:
+                raise ValueError(f'predict_em_sens: unknown outputs {sorted(unknown)}')
+            out = [o if nm in outputs else None for nm, o in zip(self.EM_SENS_OUTPUTS, out)]
         if not want_cov:
             out[1] = None
         self.lib.check(self.lib.dll.gpmpc_predict_em_sens(self.h, B, _ptr(Z), _ptr(Sigma), *[_ptr(o) for o in out]))
@@ -564,6 +572,13 @@ class Handle:
         """gpmpc_predict_sens on raw pointers; any output may be None."""
         self.lib.check(self.lib.dll.gpmpc_predict_sens(self.h, B, _ptr(z_ptr), _ptr(mean_ptr), _ptr(var_ptr), _ptr(J_ptr),
                                                        _ptr(Hm_ptr), _ptr(dvar_ptr)))
+
+    def predict_em_sens_dev(self, B, z_ptr, sigma_ptr, mean_ptr, cov_ptr, dmean_dz_ptr, dmean_dS_ptr, dcov_dz_ptr, dcov_dS_ptr):
+        """gpmpc_predict_em_sens on raw pointers; any output may be None (it lands in the handle's scratch; without cov
+        its pair sums are not formed)."""
+        self.lib.check(self.lib.dll.gpmpc_predict_em_sens(self.h, B, _ptr(z_ptr), _ptr(sigma_ptr), _ptr(mean_ptr), _ptr(cov_ptr),
+                                                          _ptr(dmean_dz_ptr), _ptr(dmean_dS_ptr), _ptr(dcov_dz_ptr),
+                                                          _ptr(dcov_dS_ptr)))
 
     def covar_dev(self, n, x_ptr, covar_ptr):
         self.lib.check(self.lib.dll.gpmpc_covar(self.h, n, _ptr(x_ptr), _ptr(covar_ptr)))
