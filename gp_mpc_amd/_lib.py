@@ -22,7 +22,7 @@ OK, EINVAL, EHIP, ENOTFIT, ENOTPD, ENOMEM = 0, -1, -2, -3, -4, -5
 METHODS = {'ME': 0, 'TA': 1, 'EM': 2, 'old_ME': 3, 'old_TA': 4}
 MEAN_FUNCS = {'zero': 0, 'const': 1, 'linear': 2, 'polynomial': 3}     # gp_functions.py:25-69
 PTR_HOST, PTR_DEVICE = 0, 1
-PHASES = ['gram', 'factor', 'solve', 'invK', 'crosscov', 'vargemm', 'finish', 'em', 'nll', 'chain']
+PHASES = ['gram', 'factor', 'solve', 'invK', 'crosscov', 'vargemm', 'finish', 'em', 'nll', 'chain', 'mc']
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -68,6 +68,8 @@ SIGNATURES = {
     'gpmpc_rollout_feedback': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gpmpc_rollout_multi': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gpmpc_rollout_multi_feedback': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int] + [_vp] * 12),
+    'gpmpc_rollout_mc': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int] + [_vp] * 12),
+    'gpmpc_randn': (ctypes.c_int, [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_int, ctypes.c_int, _vp]),
     'gpmpc_predict': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
     'gpmpc_covar': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     'gpmpc_nll': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _dp, _vp, _ip]),
@@ -163,6 +165,13 @@ class GpmpcLib:
     def set_tuning(self, name, value):
         """Diagnostic knob, e.g. set_tuning('gemm_tile', 64) pins the GEMM tile (0 = automatic)."""
         self.check(self.dll.gpmpc_set_tuning(name.encode(), int(value)))
+
+    def randn(self, seed, stream, rows, cols, device=0):
+        """[rows, cols] standard normals of gpmpc_rollout_mc's generator (Philox-4x32-10 + Box-Muller) at (seed, stream):
+        stream 0 = the initial particles, 1 + t = the draw of time step t."""
+        out = np.zeros((int(rows), int(cols)))
+        self.check(self.dll.gpmpc_randn(int(device), int(seed), int(stream), int(rows), int(cols), _ptr(out)))
+        return out
 
     # -- RCCL bootstrap of the restart shard
     def rccl_unique_id(self):
@@ -483,6 +492,29 @@ class Handle:
         self.lib.check(self.lib.dll.gpmpc_rollout_feedback(self.h, code, int(T), _ptr(z0), _ptr(Sigma0), _ptr(sa), _ptr(sb),
                                                            _ptr(Kz), _ptr(k0), _ptr(Kc), _ptr(mean), _ptr(cov), _ptr(U)))
         return mean, cov, U
+
+    def rollout_mc(self, S, T, z0, Sigma0, U=None, sa=None, sb=None, Kz=None, k0=None, seed=0, noise=False, eps0=None,
+                   eps=None, return_particles=False):
+        """Monte Carlo roll-out of S particles over T steps (gpmpc_rollout_mc, standardised units): z0[d], Sigma0[d,d],
+        U[T,Nu] (open loop) or Kz[Nu,Ny], k0[Nu] (state feedback per particle); eps0[S,d] / eps[T,S,Ny] replace the
+        generator.  Returns mean[T,Ny], cov[T,Ny,Ny] and, with return_particles, particles[T,S,Ny]."""
+        S, T, Ny, d = int(S), int(T), self.Ny, self.d
+        Nu = d - Ny
+        z0 = _f64(z0).reshape(d)
+        Sigma0 = _f64(Sigma0).reshape(d, d)
+        U = _f64(U).reshape(T, Nu) if (U is not None and Nu > 0) else None
+        sa = None if sa is None else _f64(sa).reshape(Ny)
+        sb = None if sb is None else _f64(sb).reshape(Ny)
+        Kz = None if Kz is None else _f64(Kz).reshape(Nu, Ny)
+        k0 = None if k0 is None else _f64(k0).reshape(Nu)
+        eps0 = None if eps0 is None else _f64(eps0).reshape(S, d)
+        eps = None if eps is None else _f64(eps).reshape(T, S, Ny)
+        mean, cov = np.zeros((max(T, 0), Ny)), np.zeros((max(T, 0), Ny, Ny))
+        part = np.zeros((max(T, 0), max(S, 0), Ny)) if return_particles else None
+        self.lib.check(self.lib.dll.gpmpc_rollout_mc(self.h, S, T, int(seed), int(bool(noise)), _ptr(z0), _ptr(Sigma0), _ptr(U),
+                                                     _ptr(sa), _ptr(sb), _ptr(Kz), _ptr(k0), _ptr(eps0), _ptr(eps),
+                                                     _ptr(mean), _ptr(cov), _ptr(part)))
+        return (mean, cov, part) if return_particles else (mean, cov)
 
     def predict_sens(self, Z):
         """mean[B,Ny], var[B,Ny], J[B,Ny,d] = d mean/dz, Hm[B,Ny,d,d] = d2 mean/dz2, dvar[B,Ny,d] = d var/dz."""

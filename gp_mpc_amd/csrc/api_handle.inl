@@ -15,6 +15,9 @@ struct gpmpc_gp {
     double* rollm_dev = nullptr;        // gpmpc_rollout_multi: the same for M trajectories in lock-step (grow-only)
     double* rollm_pin = nullptr;
     size_t rollm_cap = 0;
+    double* mc_dev = nullptr;           // gpmpc_rollout_mc: [inputs | particle scratch | results] (grow-only) ...
+    double* mc_pin = nullptr;           // ... and the pinned mirror of [inputs | results]
+    size_t mc_cap = 0, mc_pin_cap = 0;
     struct RollGraph { std::vector<long> key; hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; };
     std::vector<RollGraph> roll_graphs; // captured T-step loops (launch-bound at small N), keyed by everything the launches depend on
     std::vector<long> roll_warm;        // key of the last plain run: a loop is captured only after it ran once uncaptured
@@ -324,6 +327,8 @@ int gpmpc_destroy(gpmpc_gp* h) {
     hipFree(h->roll_dev);
     if (h->rollm_pin) hipHostFree(h->rollm_pin);
     hipFree(h->rollm_dev);
+    if (h->mc_pin) hipHostFree(h->mc_pin);
+    hipFree(h->mc_dev);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
     for (auto e : h->seg_events) hipEventDestroy(e);

@@ -29,6 +29,7 @@
 #include "gemm_f64_dma.hpp"
 #include "gp_kernels.hpp"
 #include "leaf64.hpp"
+#include "mc_kernels.hpp"
 #include "remove_kernels.hpp"
 #include "select_kernels.hpp"
 #include "train_native.hpp"
@@ -46,5 +47,6 @@ using namespace gpmpc;
 #include "api_remove.inl"
 #include "api_sparse.inl"
 #include "api_rollout.inl"
+#include "api_mc.inl"
 #include "api_train.inl"
 #include "api_lowlevel.inl"

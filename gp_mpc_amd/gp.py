@@ -758,6 +758,66 @@ class GP:
             var = var.clip(min=0)
         return (mean, var, controls) if return_controls else (mean, var)
 
+    def rollout_mc(self, x0, u, S=1000, seed=0, noise=False, feedback=False, x_ref=None, Q=None, R=None, K=None,
+                   eps0=None, eps=None, return_particles=False):
+        """Monte Carlo roll-out (`gpmpc_rollout_mc`): S particles drawn from the initial input distribution are propagated
+        through the GP for Nt = len(u) steps on the device, every step drawing each particle's next state from the GP's
+        predictive distribution at that particle's own input -- what the model itself predicts for the propagated
+        distribution, where 'ME', 'TA' and 'EM' collapse it to a Gaussian at every step.  Standardisation, the initial
+        covariance (eye * 1e-6 with the state block diag(sn^2)) and the gain are `rollout`'s.  Returns mean[Nt+1, Ny] and
+        var[Nt+1, Ny] (row 0 = x0; sample mean and un-standardised sample variance of the particles), with
+        return_particles=True also the un-standardised particles [Nt, S, Ny].
+
+        noise=True adds the observation noise sn^2 to every draw.  feedback=True closes the loop PER PARTICLE:
+        u = K (x_s - x_ref) on each particle's own state (the first control K (x0 - x_ref) is common), K the LQR gain of the
+        model linearised at (x0, u[0]) unless given.  eps0[S, Nx] / eps[Nt, S, Ny] replace the generator's standard normals
+        (common random numbers for comparing controllers); otherwise (seed, S) fix the result bit for bit.
+        DIFF against `rollout`: after the first step the controls are exact (the 1e-6 control block of the initial covariance
+        enters the initial particles only), and each step draws the outputs independently given the particle's input."""
+        Nx, Ny, Nu = self.__Nx, self.__Ny, self.__Nu
+        u = np.atleast_2d(np.asarray(u, dtype=np.float64))
+        Nt = u.shape[0]
+        x0 = np.asarray(x0, dtype=np.float64).reshape(Ny)
+        norm = self.__normalize
+        one = np.ones(1)
+        stdX, meanX = (np.atleast_1d(self.__stdX), np.atleast_1d(self.__meanX)) if norm else (one, 0 * one)
+        stdU, meanU = (np.atleast_1d(self.__stdU), np.atleast_1d(self.__meanU)) if norm else (one, 0 * one)
+        stdY, meanY = (np.atleast_1d(self.__stdY), np.atleast_1d(self.__meanY)) if norm else (one, 0 * one)
+        sa = stdY / stdX if norm else None                                        # x_s(next) = sa * mean_s + sb
+        sb = (meanY - meanX) / stdX if norm else None
+        covar = np.eye(Nx) * 1e-6                                                 # gp_class.py:764
+        covar[:Ny, :Ny] = np.diag(self.__hyper[:, Nx + 1] ** 2)                   # :780
+        kw = dict(sa=sa, sb=sb, seed=seed, noise=noise, eps0=eps0, eps=eps, return_particles=return_particles)
+        if feedback:
+            if Nu == 0:
+                raise ValueError('a closed-loop roll-out needs a model with controls')
+            x_ref = np.zeros(Ny) if x_ref is None else np.asarray(x_ref, dtype=np.float64).reshape(Ny)
+            if K is None:
+                Q = np.eye(Ny) if Q is None else np.asarray(Q, dtype=np.float64)
+                R = np.eye(Nu) if R is None else np.asarray(R, dtype=np.float64)
+                A, B = self.discrete_linearize(x0, u[0], covar)
+                Km = self.lqr_gain(A, B, Q, R)
+            else:
+                Km = np.asarray(K, dtype=np.float64).reshape(Nu, Ny)
+            u1 = Km @ (x0 - x_ref)
+            z0 = np.concatenate([(x0 - meanX) / stdX, (u1 - meanU) / stdU])
+            Kz = (Km * stdY[None, :]) / stdU[:, None]
+            k0 = (Km @ (meanY * np.ones(Ny) - x_ref) - meanU) / stdU
+            res = self._h.rollout_mc(S, Nt, z0, covar, Kz=Kz, k0=k0, **kw)
+        else:
+            Us = (u - meanU) / stdU
+            z0 = np.concatenate([(x0 - meanX) / stdX, Us[0]]) if Nu > 0 else (x0 - meanX) / stdX
+            res = self._h.rollout_mc(S, Nt, z0, covar, U=Us if Nu > 0 else None, **kw)
+        mean_s, cov = res[0], res[1]
+        mean, var = np.zeros((Nt + 1, Ny)), np.zeros((Nt + 1, Ny))
+        mean[0] = x0
+        mean[1:] = self.inverse_mean(mean_s, self.__meanY, self.__stdY) if norm else mean_s
+        v = np.einsum('tii->ti', cov)
+        var[1:] = (self.inverse_variance(v) if norm else v).clip(min=0)
+        if return_particles:
+            return mean, var, (self.inverse_mean(res[2], self.__meanY, self.__stdY) if norm else res[2])
+        return mean, var
+
     ROLLOUT_CLOSED_LOOP_MAX = 64    # trajectories per device call (gpmpc_rollout_multi_feedback's limit)
 
     def rollout_closed_loop(self, X0, Nt, methods=None, x_ref=None, Q=None, R=None, K=None, u0=None, return_controls=False):
@@ -841,7 +901,7 @@ class GP:
         return (mean, var, controls) if return_controls else (mean, var)
 
     def predict_compare(self, x0, u, model=None, num_cols=2, xnames=None, title=None, feedback=False, x_ref=None,
-                        Q=None, R=None, methods=None):
+                        Q=None, R=None, methods=None, mc=None):
         """`predict_compare` (gp_class.py:746-861) without its matplotlib front end: the T-step uncertainty propagation
         of every method in `methods` (default ['EM', 'TA', 'ME'], :759-760) through `GP.rollout` -- the whole horizon on
         the device -- next to the simulated trajectory of `model` when one is given (`model.sim(x0, u)`, :819-820;
@@ -852,7 +912,10 @@ class GP:
             {'t': [Nt+1], 'methods': [...], 'mean': [M, Nt+1, Ny], 'var': [M, Nt+1, Ny] (clipped at 0, :826-827),
              'y_sim': [Nt+1, Ny] or None}
 
-        num_cols, xnames, title only shaped the plot and are accepted for signature compatibility."""
+        num_cols, xnames, title only shaped the plot and are accepted for signature compatibility.
+        mc=S adds 'mc_mean' and 'mc_var' [Nt+1, Ny]: the Monte Carlo roll-out of S particles (`rollout_mc`, seed 0) under the
+        same controls or feedback arguments -- the model's own predictive distribution, against which the methods'
+        approximations can be judged.  Without it the dict is the one above, key for key."""
         u = np.atleast_2d(np.asarray(u, dtype=np.float64))
         Nt = u.shape[0]
         if methods is None:
@@ -865,8 +928,11 @@ class GP:
             if hasattr(model, 'sim'):
                 y_sim = np.vstack([np.asarray(x0, dtype=np.float64).reshape(1, -1),
                                    np.asarray(model.sim(x0, u), dtype=np.float64).reshape(Nt, -1)])   # :819-820
-        return {'t': np.linspace(0.0, Nt * dt, Nt + 1), 'methods': list(methods), 'mean': mean, 'var': var.clip(min=0),
-                'y_sim': y_sim}
+        out = {'t': np.linspace(0.0, Nt * dt, Nt + 1), 'methods': list(methods), 'mean': mean, 'var': var.clip(min=0),
+               'y_sim': y_sim}
+        if mc is not None:
+            out['mc_mean'], out['mc_var'] = self.rollout_mc(x0, u, S=int(mc), feedback=feedback, x_ref=x_ref, Q=Q, R=R)
+        return out
 
     def close(self):
         if self._h is not None:

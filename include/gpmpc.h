@@ -65,7 +65,8 @@ extern "C" {
 #define GPMPC_PH_EM 7         /* exact-moment N x N pair tiles               */
 #define GPMPC_PH_NLL 8        /* NLL reductions + gradient pass              */
 #define GPMPC_PH_CHAIN 9      /* the persistent chain kernel alone = the Cholesky without the inverse (inside FACTOR) */
-#define GPMPC_PH_COUNT 10
+#define GPMPC_PH_MC 10        /* Monte Carlo roll-out: particle init, hand-over and moment kernels (not its predictions) */
+#define GPMPC_PH_COUNT 11
 
 typedef struct gpmpc_gp gpmpc_gp; /* opaque model handle */
 
@@ -308,6 +309,39 @@ int gpmpc_rollout_multi_feedback(gpmpc_gp* h, int M, const int* methods, int T, 
                                  const double* sa, const double* sb, const int* closed, const double* Kz,
                                  const double* k0, const double* Kc, const double* U, double* mean, double* cov,
                                  double* U_out);
+/* Monte Carlo roll-out: S particles propagated through the GP for T steps on the device -- what the GP itself predicts for
+ * the propagated distribution, next to the moment-matching methods above, which collapse it to a Gaussian at every step
+ * (no reference counterpart; predict_compare, gp_class.py:746-861, compares them with one simulated trajectory only).
+ * Host pointers, standardised units; z0[d], Sigma0[d x d], U[T x Nu], sa / sb[Ny], Kz[Nu x Ny], k0[Nu] exactly as in
+ * gpmpc_rollout / gpmpc_rollout_feedback.  Particle s starts at z_s = z0 + L0 eps0_s, L0 a lower-triangular factor of
+ * Sigma0 formed on the host (a semidefinite Sigma0 is fine: a pivot below d eps max(diag) gives a zero column; an
+ * indefinite one is GPMPC_EINVAL).  Step t: (m_s, v_s) = gpmpc_predict_mean_var at z_s for all S particles (in chunks of the
+ * predict family's size, gpmpc_set_tuning "predict_chunk"), then
+ *   y_s = m_s + sqrt(max(v_s, 0) + noise sn^2) eps_{t,s}      (noise != 0 adds the observation noise of hyper's sn)
+ * and the next input z_s = [sa y_s + sb, u]: open loop u = U[t + 1] (U[0] is not read: the first control comes with z0, as
+ * in gpmpc_rollout), closed loop (Kz != NULL; U is ignored) u = Kz y_s + k0 PER PARTICLE -- gpmpc_rollout_feedback's
+ * convention applied to every trajectory of its own.  Outputs: mean[T x Ny] and cov[T x Ny x Ny], the sample mean and the
+ * unbiased sample covariance of the S vectors y_s of each step (S = 1: cov = 0), and, unless NULL, particles[T x S x Ny].
+ * The moments are reduced in two passes (mean, then centred products) over fixed blocks of 256 particles combined in a
+ * fixed order, without atomics: a function of the data only.
+ * Random numbers: eps0_s[d] and eps_{t,s}[Ny] are standard normals from a counter-based generator, Philox-4x32-10 with
+ * key = the two halves of `seed` and counter = (row s, column pair, stream, 0), stream 0 for eps0 and 1 + t for step t;
+ * the four words give two 53-bit uniforms in (0, 1], Box-Muller the normals of columns 2j (cosine) and 2j + 1 (sine):
+ * gpmpc_randn returns exactly these arrays.  A value depends on (seed, stream, row, column) only -- not on S, the launch
+ * geometry or the chunking -- so a call is reproducible bit for bit.  eps0[S x d] and eps[T x S x Ny] (each may be NULL)
+ * REPLACE the generator: common random numbers for comparing controllers, and an exact replay; `seed` is then unused.
+ * Each step draws the outputs INDEPENDENTLY given the particle's input (and independently per output): that is the
+ * assumption the moment methods approximate; it is not a consistent draw of one function over the horizon.
+ * DIFF: after step 0 the controls are exact.  gpmpc_rollout keeps the control block of Sigma0 in every step's input
+ * covariance; here Sigma0 -- its control block included -- enters the initial particles only.
+ * Everything runs on the handle's stream, one upload and one download per call, no graph capture.  A FITC handle and a
+ * prior mean added to the prediction work unchanged.  GPMPC_EINVAL: the rules of gpmpc_rollout, S < 1, S > 2^20, a closed
+ * loop with Nu = 0 or k0 == NULL; GPMPC_ENOTFIT without factors; the handle stays usable. */
+int gpmpc_rollout_mc(gpmpc_gp* h, int S, int T, unsigned long long seed, int noise, const double* z0,
+                     const double* Sigma0, const double* U, const double* sa, const double* sb, const double* Kz,
+                     const double* k0, const double* eps0, const double* eps, double* mean, double* cov, double* particles);
+/* out[rows x cols] (HOST pointer): the standard normals of gpmpc_rollout_mc's generator at (seed, stream, row, column). */
+int gpmpc_randn(int device, unsigned long long seed, unsigned stream, int rows, int cols, double* out);
 /* a14 GP.covar gp_class.py:353-381: covar[Ny x n x n] = sf^2 - V^T V for n new inputs. */
 int gpmpc_covar(gpmpc_gp* h, int n, const double* Xnew, double* covar);
 
