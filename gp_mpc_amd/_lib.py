@@ -70,6 +70,12 @@ SIGNATURES = {
     'gpmpc_rollout_multi_feedback': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int] + [_vp] * 12),
     'gpmpc_rollout_mc': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int] + [_vp] * 12),
     'gpmpc_randn': (ctypes.c_int, [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_int, ctypes.c_int, _vp]),
+    'gpmpc_paths_draw': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, _vp, _vp, _vp]),
+    'gpmpc_paths_get': (ctypes.c_int, [_vp, _ip, _ip, _vp, _vp, _vp]),
+    'gpmpc_paths_eval': (ctypes.c_int, [_vp, _vp, _vp]),
+    'gpmpc_paths_eval_grid': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
+    'gpmpc_paths_free': (ctypes.c_int, [_vp]),
+    'gpmpc_rollout_paths': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int] + [_vp] * 12),
     'gpmpc_predict': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
     'gpmpc_covar': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     'gpmpc_nll': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _dp, _vp, _ip]),
@@ -514,6 +520,73 @@ class Handle:
         self.lib.check(self.lib.dll.gpmpc_rollout_mc(self.h, S, T, int(seed), int(bool(noise)), _ptr(z0), _ptr(Sigma0), _ptr(U),
                                                      _ptr(sa), _ptr(sb), _ptr(Kz), _ptr(k0), _ptr(eps0), _ptr(eps),
                                                      _ptr(mean), _ptr(cov), _ptr(part)))
+        return (mean, cov, part) if return_particles else (mean, cov)
+
+    # -- pathwise posterior samples (gpmpc_paths_*): S functions drawn once, then evaluated wherever a particle goes
+    def paths_draw(self, S, F, seed=0, eps_omega=None, w=None, xi=None):
+        """Draw S paths of F random features (F even) onto the handle; eps_omega[Ny,F/2,d], w[Ny,S,F], xi[Ny,S,N] replace the
+        generator's streams 0x40000000 + a / 0x50000000 + a / 0x60000000 + a, each on its own."""
+        S, F = int(S), int(F)
+        eps_omega = None if eps_omega is None else _f64(eps_omega).reshape(self.Ny, F // 2, self.d)
+        w = None if w is None else _f64(w).reshape(self.Ny, S, F)
+        xi = None if xi is None else _f64(xi).reshape(self.Ny, S, self.N)
+        self.lib.check(self.lib.dll.gpmpc_paths_draw(self.h, S, F, int(seed), _ptr(eps_omega), _ptr(w), _ptr(xi)))
+
+    def paths_size(self):
+        """(S, F) of the drawn paths."""
+        S, F = ctypes.c_int(0), ctypes.c_int(0)
+        self.lib.check(self.lib.dll.gpmpc_paths_get(self.h, ctypes.byref(S), ctypes.byref(F), None, None, None))
+        return S.value, F.value
+
+    def paths_get(self, omega=True, w=True, v=True):
+        """dict(S, F, omega[Ny,F/2,d] (already / ell), w[Ny,S,F], v[Ny,S,N]) of the drawn paths."""
+        S, F = self.paths_size()
+        om = np.zeros((self.Ny, F // 2, self.d)) if omega else None
+        ww = np.zeros((self.Ny, S, F)) if w else None
+        vv = np.zeros((self.Ny, S, self.N)) if v else None
+        self.lib.check(self.lib.dll.gpmpc_paths_get(self.h, None, None, _ptr(om), _ptr(ww), _ptr(vv)))
+        return dict(S=S, F=F, omega=om, w=ww, v=vv)
+
+    def paths_eval(self, Z):
+        """f[S,Ny]: path s at its own input Z[s] (Z[S,d], standardised units)."""
+        S, _ = self.paths_size()
+        Z = _f64(Z).reshape(S, self.d)
+        f = np.zeros((S, self.Ny))
+        self.lib.check(self.lib.dll.gpmpc_paths_eval(self.h, _ptr(Z), _ptr(f)))
+        return f
+
+    def paths_eval_grid(self, Z):
+        """f[S,B,Ny]: every path at the common points Z[B,d]."""
+        S, _ = self.paths_size()
+        Z = _f64(Z).reshape(-1, self.d)
+        f = np.zeros((S, Z.shape[0], self.Ny))
+        self.lib.check(self.lib.dll.gpmpc_paths_eval_grid(self.h, Z.shape[0], _ptr(Z), _ptr(f)))
+        return f
+
+    def paths_free(self):
+        self.lib.check(self.lib.dll.gpmpc_paths_free(self.h))
+
+    def rollout_paths(self, T, z0, Sigma0, U=None, sa=None, sb=None, Kz=None, k0=None, seed=0, noise=False, eps0=None, eps=None,
+                      return_particles=False):
+        """rollout_mc with particle s following the drawn path s (gpmpc_rollout_paths; S is the drawn S): returns mean[T,Ny],
+        cov[T,Ny,Ny] and, with return_particles, particles[T,S,Ny]."""
+        S, _ = self.paths_size()
+        T, Ny, d = int(T), self.Ny, self.d
+        Nu = d - Ny
+        z0 = _f64(z0).reshape(d)
+        Sigma0 = _f64(Sigma0).reshape(d, d)
+        U = _f64(U).reshape(T, Nu) if (U is not None and Nu > 0) else None
+        sa = None if sa is None else _f64(sa).reshape(Ny)
+        sb = None if sb is None else _f64(sb).reshape(Ny)
+        Kz = None if Kz is None else _f64(Kz).reshape(Nu, Ny)
+        k0 = None if k0 is None else _f64(k0).reshape(Nu)
+        eps0 = None if eps0 is None else _f64(eps0).reshape(S, d)
+        eps = None if eps is None else _f64(eps).reshape(T, S, Ny)
+        mean, cov = np.zeros((max(T, 0), Ny)), np.zeros((max(T, 0), Ny, Ny))
+        part = np.zeros((max(T, 0), S, Ny)) if return_particles else None
+        self.lib.check(self.lib.dll.gpmpc_rollout_paths(self.h, T, int(seed), int(bool(noise)), _ptr(z0), _ptr(Sigma0), _ptr(U),
+                                                        _ptr(sa), _ptr(sb), _ptr(Kz), _ptr(k0), _ptr(eps0), _ptr(eps),
+                                                        _ptr(mean), _ptr(cov), _ptr(part)))
         return (mean, cov, part) if return_particles else (mean, cov)
 
     def predict_sens(self, Z):

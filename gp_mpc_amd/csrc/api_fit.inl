@@ -165,6 +165,7 @@ static int fit_impl(gpmpc_gp* h, const double* hyper, int want_invK, int* info, 
     h->fitted = false;
     h->have_invK = false;
     h->have_beta = false;
+    ++h->factor_gen;
     h->tail.armed = false;
     int post_rc = GPMPC_OK;
     std::vector<double> kpart;           // [Ny][d+2]; y - m(X) goes to h->Yc (optimize.py:285,494)
@@ -294,6 +295,7 @@ extern "C" int gpmpc_append(gpmpc_gp* h, int n, const double* Xnew, const double
         free_predict_scratch(h);
         h->XT = XT1; h->Y = Y1; h->ws = ws1;
         h->N = N1; h->Np = Np1;
+        ++h->factor_gen;                                    // (drawn paths belong to the old data: api_paths.inl)
         h->have_invK = false;
         const size_t need = seg_event_count(Np1);
         while (h->seg_events.size() < need) {
@@ -334,6 +336,7 @@ extern "C" int gpmpc_append(gpmpc_gp* h, int n, const double* Xnew, const double
         h->fitted = true;
         h->have_invK = invK0;
         h->have_beta = false;
+        ++h->factor_gen;
         refresh_residual(h);
         g_err = keep;
         return rc;
@@ -464,6 +467,7 @@ extern "C" int gpmpc_set_factors(gpmpc_gp* h, const double* hyper, const double*
     h->fitted = false;
     h->have_invK = false;
     h->have_beta = false;
+    ++h->factor_gen;
     h->hyper.assign(hyper, hyper + (size_t)h->Ny * h->nh());
     std::vector<double> kpart;
     CHK(upload_mean_and_residual(h, hyper, h->Ny, kpart, &h->mpar, h->Y, &h->Yc));

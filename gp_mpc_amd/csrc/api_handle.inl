@@ -18,6 +18,15 @@ struct gpmpc_gp {
     double* mc_dev = nullptr;           // gpmpc_rollout_mc: [inputs | particle scratch | results] (grow-only) ...
     double* mc_pin = nullptr;           // ... and the pinned mirror of [inputs | results]
     size_t mc_cap = 0, mc_pin_cap = 0;
+    // pathwise posterior samples (api_paths.inl, paths_kernels.hpp): S paths of F features, valid while p_gen == factor_gen
+    long factor_gen = 0;                // counts the calls that changed (or dropped) the factors or the data
+    long p_gen = -1;
+    int pS = 0, pSld = 0, pF = 0, pFp = 0;
+    double *pV = nullptr, *pWT = nullptr, *pOmega = nullptr, *pPart = nullptr;   // [Ny][Np][Sld], [Ny][Fp][Sld], [Ny][F/2][d], partial sums (grow-only)
+    size_t pV_cap = 0, pWT_cap = 0, pOmega_cap = 0, pPart_cap = 0;
+    double* pio_dev = nullptr;          // gpmpc_paths_eval / gpmpc_rollout_paths: [inputs | scratch | results] (grow-only) ...
+    double* pio_pin = nullptr;          // ... and the pinned mirror of [inputs | results]
+    size_t pio_cap = 0, pio_pin_cap = 0;
     struct RollGraph { std::vector<long> key; hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; };
     std::vector<RollGraph> roll_graphs; // captured T-step loops (launch-bound at small N), keyed by everything the launches depend on
     std::vector<long> roll_warm;        // key of the last plain run: a loop is captured only after it ran once uncaptured
@@ -329,6 +338,9 @@ int gpmpc_destroy(gpmpc_gp* h) {
     hipFree(h->rollm_dev);
     if (h->mc_pin) hipHostFree(h->mc_pin);
     hipFree(h->mc_dev);
+    hipFree(h->pV); hipFree(h->pWT); hipFree(h->pOmega); hipFree(h->pPart);
+    if (h->pio_pin) hipHostFree(h->pio_pin);
+    hipFree(h->pio_dev);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
     for (auto e : h->seg_events) hipEventDestroy(e);
@@ -367,6 +379,7 @@ int gpmpc_set_mean_func(gpmpc_gp* h, int kind, int add_to_prediction) {
     h->fitted = false;
     h->have_invK = false;
     h->have_beta = false;
+    ++h->factor_gen;
     return GPMPC_OK;
 }
 

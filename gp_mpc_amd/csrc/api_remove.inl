@@ -149,6 +149,7 @@ extern "C" int gpmpc_remove(gpmpc_gp* h, int n, const int* idx) {
         h->fitted = true;
         h->have_invK = invK0;
         h->have_beta = false;
+        ++h->factor_gen;
         refresh_residual(h);
         g_err = keep;
         return rc;
@@ -194,6 +195,7 @@ extern "C" int gpmpc_remove(gpmpc_gp* h, int n, const int* idx) {
     h->XT = nw.XT; h->Y = nw.Y; h->ws = nw.ws;
     nw.keep = true;
     h->N = N1; h->Np = Np1;
+    ++h->factor_gen;                                        // (drawn paths belong to the old data: api_paths.inl)
     h->have_invK = false;
     ++h->n_remove_down;
     CHK(refresh_residual(h));

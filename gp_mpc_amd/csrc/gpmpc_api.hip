@@ -30,6 +30,7 @@
 #include "gp_kernels.hpp"
 #include "leaf64.hpp"
 #include "mc_kernels.hpp"
+#include "paths_kernels.hpp"
 #include "remove_kernels.hpp"
 #include "select_kernels.hpp"
 #include "train_native.hpp"
@@ -48,5 +49,6 @@ using namespace gpmpc;
 #include "api_sparse.inl"
 #include "api_rollout.inl"
 #include "api_mc.inl"
+#include "api_paths.inl"
 #include "api_train.inl"
 #include "api_lowlevel.inl"

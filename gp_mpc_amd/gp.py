@@ -774,6 +774,13 @@ class GP:
         (common random numbers for comparing controllers); otherwise (seed, S) fix the result bit for bit.
         DIFF against `rollout`: after the first step the controls are exact (the 1e-6 control block of the initial covariance
         enters the initial particles only), and each step draws the outputs independently given the particle's input."""
+        kw = dict(seed=seed, noise=noise, eps0=eps0, eps=eps, return_particles=return_particles)
+        return self._particle_rollout(lambda Nt, z0, covar, **a: self._h.rollout_mc(S, Nt, z0, covar, **a, **kw), x0, u,
+                                      feedback, x_ref, Q, R, K, return_particles)
+
+    def _particle_rollout(self, run, x0, u, feedback, x_ref, Q, R, K, return_particles):
+        """What `rollout_mc` and `rollout_paths` share: standardisation, the initial covariance, the gain, and the
+        un-standardised moments (and particles) of `run(Nt, z0, covar, sa=, sb=, U= | Kz=, k0=)`."""
         Nx, Ny, Nu = self.__Nx, self.__Ny, self.__Nu
         u = np.atleast_2d(np.asarray(u, dtype=np.float64))
         Nt = u.shape[0]
@@ -787,7 +794,6 @@ class GP:
         sb = (meanY - meanX) / stdX if norm else None
         covar = np.eye(Nx) * 1e-6                                                 # gp_class.py:764
         covar[:Ny, :Ny] = np.diag(self.__hyper[:, Nx + 1] ** 2)                   # :780
-        kw = dict(sa=sa, sb=sb, seed=seed, noise=noise, eps0=eps0, eps=eps, return_particles=return_particles)
         if feedback:
             if Nu == 0:
                 raise ValueError('a closed-loop roll-out needs a model with controls')
@@ -803,11 +809,11 @@ class GP:
             z0 = np.concatenate([(x0 - meanX) / stdX, (u1 - meanU) / stdU])
             Kz = (Km * stdY[None, :]) / stdU[:, None]
             k0 = (Km @ (meanY * np.ones(Ny) - x_ref) - meanU) / stdU
-            res = self._h.rollout_mc(S, Nt, z0, covar, Kz=Kz, k0=k0, **kw)
+            res = run(Nt, z0, covar, sa=sa, sb=sb, Kz=Kz, k0=k0)
         else:
             Us = (u - meanU) / stdU
             z0 = np.concatenate([(x0 - meanX) / stdX, Us[0]]) if Nu > 0 else (x0 - meanX) / stdX
-            res = self._h.rollout_mc(S, Nt, z0, covar, U=Us if Nu > 0 else None, **kw)
+            res = run(Nt, z0, covar, sa=sa, sb=sb, U=Us if Nu > 0 else None)
         mean_s, cov = res[0], res[1]
         mean, var = np.zeros((Nt + 1, Ny)), np.zeros((Nt + 1, Ny))
         mean[0] = x0
@@ -817,6 +823,39 @@ class GP:
         if return_particles:
             return mean, var, (self.inverse_mean(res[2], self.__meanY, self.__stdY) if norm else res[2])
         return mean, var
+
+    # ------------------------------------------------------------------ pathwise posterior samples
+    def sample_paths(self, S, F=1024, seed=0):
+        """Draw S functions from the posterior onto the device (`gpmpc_paths_draw`: pathwise conditioning with F random
+        features of the prior, F even).  They stay valid until the data or the hyper-parameters change; `paths_eval`
+        evaluates them.  F trades the prior's approximation error ("Pathwise samples") against the setup's
+        N F S product."""
+        self._refuse_sparse('sample_paths')
+        self._h.paths_draw(S, F, seed=seed)
+
+    def paths_eval(self, Z, grid=False):
+        """The drawn paths at inputs Z in the object's units ([x, u] rows, standardised here like `predict`), outputs
+        un-standardised like `predict_batch`.  grid=False: Z[S, Nx], path s at its own row, returns [S, Ny]; grid=True:
+        every path at the common points Z[B, Nx], returns [S, B, Ny] (Thompson-sampling draws, plots)."""
+        self._refuse_sparse('paths_eval')
+        Z = np.asarray(Z, dtype=np.float64).reshape(-1, self.__Nx)
+        if self.__normalize:
+            Z = self.standardize(Z, self.__meanZ, self.__stdZ)
+        f = self._h.paths_eval_grid(Z) if grid else self._h.paths_eval(Z)
+        return self.inverse_mean(f, self.__meanY, self.__stdY) if self.__normalize else f
+
+    def rollout_paths(self, x0, u, S=1000, F=1024, seed=0, noise=False, feedback=False, x_ref=None, Q=None, R=None, K=None,
+                      eps0=None, eps=None, return_particles=False):
+        """Consistent Monte Carlo roll-out (`gpmpc_rollout_paths`): `rollout_mc` with every particle propagated through ONE
+        function drawn from the posterior (`sample_paths(S, F, seed)`, drawn here), so a particle that returns to a state
+        sees the same dynamics there and the trajectories carry the temporal correlation the independent per-step draws
+        of `rollout_mc` lose.  noise=True adds the observation noise sn eps to every step.  Arguments and return values are
+        `rollout_mc`'s."""
+        self._refuse_sparse('rollout_paths')
+        self._h.paths_draw(S, F, seed=seed)
+        kw = dict(seed=seed, noise=noise, eps0=eps0, eps=eps, return_particles=return_particles)
+        return self._particle_rollout(lambda Nt, z0, covar, **a: self._h.rollout_paths(Nt, z0, covar, **a, **kw), x0, u,
+                                      feedback, x_ref, Q, R, K, return_particles)
 
     ROLLOUT_CLOSED_LOOP_MAX = 64    # trajectories per device call (gpmpc_rollout_multi_feedback's limit)
 
@@ -901,7 +940,7 @@ class GP:
         return (mean, var, controls) if return_controls else (mean, var)
 
     def predict_compare(self, x0, u, model=None, num_cols=2, xnames=None, title=None, feedback=False, x_ref=None,
-                        Q=None, R=None, methods=None, mc=None):
+                        Q=None, R=None, methods=None, mc=None, mc_paths=None):
         """`predict_compare` (gp_class.py:746-861) without its matplotlib front end: the T-step uncertainty propagation
         of every method in `methods` (default ['EM', 'TA', 'ME'], :759-760) through `GP.rollout` -- the whole horizon on
         the device -- next to the simulated trajectory of `model` when one is given (`model.sim(x0, u)`, :819-820;
@@ -915,7 +954,8 @@ class GP:
         num_cols, xnames, title only shaped the plot and are accepted for signature compatibility.
         mc=S adds 'mc_mean' and 'mc_var' [Nt+1, Ny]: the Monte Carlo roll-out of S particles (`rollout_mc`, seed 0) under the
         same controls or feedback arguments -- the model's own predictive distribution, against which the methods'
-        approximations can be judged.  Without it the dict is the one above, key for key."""
+        approximations can be judged.  Without it the dict is the one above, key for key.  mc_paths=F (with mc=S) takes the
+        consistent roll-out instead (`rollout_paths`: S functions of F features drawn once)."""
         u = np.atleast_2d(np.asarray(u, dtype=np.float64))
         Nt = u.shape[0]
         if methods is None:
@@ -931,7 +971,11 @@ class GP:
         out = {'t': np.linspace(0.0, Nt * dt, Nt + 1), 'methods': list(methods), 'mean': mean, 'var': var.clip(min=0),
                'y_sim': y_sim}
         if mc is not None:
-            out['mc_mean'], out['mc_var'] = self.rollout_mc(x0, u, S=int(mc), feedback=feedback, x_ref=x_ref, Q=Q, R=R)
+            if mc_paths is None:
+                out['mc_mean'], out['mc_var'] = self.rollout_mc(x0, u, S=int(mc), feedback=feedback, x_ref=x_ref, Q=Q, R=R)
+            else:
+                out['mc_mean'], out['mc_var'] = self.rollout_paths(x0, u, S=int(mc), F=int(mc_paths), feedback=feedback,
+                                                                   x_ref=x_ref, Q=Q, R=R)
         return out
 
     def close(self):

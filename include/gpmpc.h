@@ -342,6 +342,56 @@ int gpmpc_rollout_mc(gpmpc_gp* h, int S, int T, unsigned long long seed, int noi
                      const double* k0, const double* eps0, const double* eps, double* mean, double* cov, double* particles);
 /* out[rows x cols] (HOST pointer): the standard normals of gpmpc_rollout_mc's generator at (seed, stream, row, column). */
 int gpmpc_randn(int device, unsigned long long seed, unsigned stream, int rows, int cols, double* out);
+
+/* ---- pathwise posterior samples: consistent Monte Carlo roll-outs -------------------------------- */
+/* S functions drawn ONCE from the posterior and then evaluated wherever a particle goes: a particle that returns to a state
+ * sees the same dynamics there, which gpmpc_rollout_mc's independent per-step draws do not give.  Pathwise conditioning
+ * (Matheron's rule) with a random-feature prior (Wilson, Borovitskiy, Terenin, Mostowsky, Deisenroth: "Efficiently sampling
+ * functions from Gaussian process posteriors", ICML 2020), per output a with hyper row (ell, sf, sn), standardised units:
+ *   frequencies  omega_j = eps_j / ell (elementwise), eps_j ~ N(0, I_d), j < F / 2, shared by all paths;
+ *   features     phi_2j(z) = c cos(omega_j . z), phi_2j+1(z) = c sin(omega_j . z), c = sf sqrt(2 / F)   (E[phi(z) . phi(z')] = k(z, z'));
+ *   per path s   w_s ~ N(0, I_F), xi_s ~ N(0, I_N),  v_s = alpha - K^-1 (Phi w_s + sn xi_s),  Phi = phi(X) [N x F],  K^-1 r = L^-T (L^-1 r);
+ *   the path     f_s(z) = m(z) + phi(z) . w_s + sum_i v_s,i k(z, x_i)
+ * with the prior mean m added exactly when the handle adds it to a prediction: w = 0, xi = 0 gives gpmpc_predict_mean_var's
+ * mean.  Exact given the frequencies: the data term; approximate: the prior, by its F features ("Pathwise samples",
+ * has the closed-form covariance of f_s - mean for a given omega and how it approaches the posterior covariance with F).
+ * Random streams of gpmpc_randn's generator, a value depending on (seed, stream, row, column) only: */
+#define GPMPC_PATHS_STREAM_OMEGA 0x40000000u   /* + a: eps_a, row j, d columns  */
+#define GPMPC_PATHS_STREAM_W 0x50000000u       /* + a: w_a, row s, F columns    */
+#define GPMPC_PATHS_STREAM_XI 0x60000000u      /* + a: xi_a, row s, N columns   */
+/* (streams 0 and 1 + t keep their roll-out meaning).  Host pointers throughout, everything on the handle's stream.
+ * gpmpc_paths_draw: draws S paths of F features (F even, the same for all outputs); eps_omega[Ny x F/2 x d], w[Ny x S x F],
+ * xi[Ny x S x N] (each may be NULL) REPLACE the generator per array.  Cost: the features, then per output the products
+ * Phi W^T, L^-1 R and L^-T T1 on the fp64 matrix cores, O(N (F + N) S).  The paths live on the handle in grow-only device
+ * buffers: Ny Np S doubles of weights (S rounded up to even; Np = N rounded up to 64), Ny F S of feature weights; scratch of
+ * the setup is released before the call returns.  They are released by gpmpc_paths_free (with the staging of the eval / roll-out
+ * calls) / gpmpc_destroy, and every call that
+ * changes or drops the factors or the data (gpmpc_fit, gpmpc_fit_predict_mean_var, gpmpc_append*, gpmpc_remove,
+ * gpmpc_set_factors, gpmpc_set_mean_func, gpmpc_train_multistart) makes them STALE: the calls below then return
+ * GPMPC_EINVAL until paths are drawn again.  GPMPC_EINVAL: S outside 1 .. 2^20, F odd, < 2 or > 65536, a FITC handle (a sample
+ * of its predictor is another construction); GPMPC_ENOTFIT without factors; after these the handle stays usable and earlier
+ * paths stay valid.  GPMPC_ENOMEM: a device allocation failed; earlier paths stay valid unless
+ * one of their own buffers had to grow for this call. */
+int gpmpc_paths_draw(gpmpc_gp* h, int S, int F, unsigned long long seed, const double* eps_omega, const double* w,
+                     const double* xi);
+/* What was drawn (any pointer may be NULL): S, F, omega[Ny x F/2 x d] (already divided by ell), w[Ny x S x F], v[Ny x S x N]. */
+int gpmpc_paths_get(gpmpc_gp* h, int* S, int* F, double* omega, double* w, double* v);
+/* f[S x Ny]: path s at its own input Z[s] (Z[S x d]).  One pass over the weights: the training points are cut into fixed
+ * blocks of 128 and the frequencies into blocks of 16, partial sums per (block, path, output) are added in a fixed order:
+ * the result is a function of the data only. */
+int gpmpc_paths_eval(gpmpc_gp* h, const double* Z, double* f);
+/* f[S x B x Ny]: all paths at the common points Z[B x d] (Thompson-sampling draws, plots): cross-covariances and two
+ * matrix products, in chunks of the predict family's size. */
+int gpmpc_paths_eval_grid(gpmpc_gp* h, int B, const double* Z, double* f);
+int gpmpc_paths_free(gpmpc_gp* h);
+/* gpmpc_rollout_mc with the step replaced: particle s follows path s (S is the drawn S), y_s = f_s(z_s) + noise sn eps_{t,s}
+ * with eps from stream 1 + t or the caller's eps[T x S x Ny] (noise == 0 draws nothing after step 0), the initial particles
+ * z_s = z0 + L0 eps0_s from stream 0 (the same `seed` gives gpmpc_rollout_mc's initial particles) or eps0[S x d]; every other
+ * argument, the semidefinite Sigma0, the hand-over, the moment reduction and the outputs are gpmpc_rollout_mc's.  A step
+ * reads the path weights once and forms no variance.  GPMPC_EINVAL also without valid paths. */
+int gpmpc_rollout_paths(gpmpc_gp* h, int T, unsigned long long seed, int noise, const double* z0, const double* Sigma0,
+                        const double* U, const double* sa, const double* sb, const double* Kz, const double* k0,
+                        const double* eps0, const double* eps, double* mean, double* cov, double* particles);
 /* a14 GP.covar gp_class.py:353-381: covar[Ny x n x n] = sf^2 - V^T V for n new inputs. */
 int gpmpc_covar(gpmpc_gp* h, int n, const double* Xnew, double* covar);
 
